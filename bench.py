@@ -19,6 +19,11 @@ same inside-outside model (values in [0,1], background 0).
     python bench.py [--gpus N --steps K --warmup W]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit,
+ms_per_step, ...).  --full adds what takes runs of its own after the timed region: the probe
+kernel's in-graph clock and the roofline fields, the fused-loss timing and the CPU baselines.
+--dump-outputs DIR writes what the last timed step computed (step_outputs) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -203,6 +208,39 @@ class Trainer:
     def probe_flops(self):
         _, N, C, H, K, R, s = self.probe_key()
         return conv_flops(N, C, H, K, R, s)
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of the parameter / gradient vectors (8 MB each as float32)
+
+
+def step_outputs(tr, loss):
+    """What a caller of Trainer.step() holds after a step, as float32 arrays: the loss it returns and
+    the state it leaves behind — the parameters after the Adam update, their gradients (as the step
+    leaves them in .grad: loss-scaled under fp16) and the BatchNorm running statistics.  The
+    parameter and gradient vectors (every parameter flattened, in net.parameters() order) are cut to
+    the same fixed sample of DUMP_SAMPLE positions (seeded, sorted), so two builds dump the same
+    positions."""
+    ps = list(tr.net.parameters())
+    n = sum(p.numel() for p in ps)
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(tr.dev)
+
+    def sample(ts):
+        return torch.cat([t.detach().float().reshape(-1) for t in ts]).index_select(0, idx).cpu().numpy()
+
+    bufs = [b for _, b in sorted(tr.net.named_buffers()) if b.is_floating_point()]
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+           "params": sample(ps),
+           "grads": sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in ps])}
+    if bufs:
+        out["bn_running_stats"] = torch.cat([b.detach().float().reshape(-1) for b in bufs]).cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _clock_spans_ms(clk, rows):
@@ -469,11 +507,17 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5), help="BASELINE.json config (module doc)")
     ap.add_argument("--render", type=int, default=0, help="ImplicitLoss render size R (0 = the config's)")
     ap.add_argument("--dtype", default="", choices=("", "bf16", "fp16"), help="compute dtype (default: the config's)")
-    ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU-baseline steps (0 = skip; 5 ≈ 11 s at 16 threads)")
-    ap.add_argument("--cpu1-steps", type=int, default=5, help="timed config-1 CPU steps (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the probe kernel (its clock is armed in the step "
+                         "graph) and the roofline fields, the fused-loss call and the CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (step_outputs) as DIR/<name>.npy")
+    ap.add_argument("--cpu-steps", type=int, default=5,
+                    help="with --full: timed CPU-baseline steps (0 = skip; 5 ≈ 11 s at 16 threads)")
+    ap.add_argument("--cpu1-steps", type=int, default=5, help="with --full: timed config-1 CPU steps (0 = skip)")
     ap.add_argument("--profile", action="store_true",
-                    help="rocprof mode: nothing runs after the timed region (no probe / loss timing / CPU "
-                         "baseline), so the last --steps step graphs of the trace are the timed ones")
+                    help="rocprof mode: nothing runs after the timed region even with --full (no probe / loss "
+                         "timing / CPU baseline), so the last --steps step graphs of the trace are the timed ones")
     ap.add_argument("--dp-rehearsal", action="store_true",
                     help="N=1 only: run the data-parallel machinery (captured RCCL all-reduce) on a world-1 group")
     ap.add_argument("--dp-overlap", type=int, default=1, choices=(0, 1),
@@ -528,6 +572,7 @@ def run(args, json_fd):
     from sqr import dist
     rank, world = dist.env()[:2]
     cuda = args.device == "cuda"
+    extras = args.full and not args.profile and cuda  # the measurements beyond the headline figure
     try:
         if cuda:
             rank, world, dev = dist.init("nccl")
@@ -543,7 +588,7 @@ def run(args, json_fd):
                      dp_bucket_mb=args.dp_bucket_mb or None)
         B, H, R = tr.B, tr.H, tr.R
         probe_clock = None
-        if tr.use_graph and not args.profile:
+        if tr.use_graph and extras:
             probe_clock = torch.empty(N_PROBE_SLOTS, 2, dtype=torch.int64, device=dev)
             _clock_reset(probe_clock)
         tr.capture(probe_clock)
@@ -573,6 +618,8 @@ def run(args, json_fd):
     dt = dist.max_over_ranks(dt_rank)
     per_rank_ms = [v / args.steps * 1e3 for v in dist.gather_over_ranks(dt_rank)]
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(tr, loss))
     value = B * world * args.steps / dt
     dname = {torch.bfloat16: "bf16", torch.float16: "fp16", torch.float32: "fp32"}[tr.dtype]
 
@@ -608,7 +655,7 @@ def run(args, json_fd):
     if tr.scaler is not None:
         out["loss_scale"] = float(tr.scaler.get_scale())
 
-    if not args.profile and cuda:
+    if extras:
         kern_ms, nlaunch, how = time_probe(tr)
         flops = tr.probe_flops()
         achieved = flops / (kern_ms * 1e-3) / 1e12 if nlaunch else None

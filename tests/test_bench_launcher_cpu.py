@@ -64,6 +64,28 @@ def test_one_gpu_runs_in_process():
     assert "launching" not in err
 
 
+@pytest.mark.timeout(300)
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs DIR: float32 .npy files of what the last timed step computed (the loss the result
+    line reports, parameters, gradients, BatchNorm statistics); a plain run carries none of --full's
+    fields."""
+    import numpy as np
+    out = tmp_path / "dump"
+    rc, lines, err = _run(["--gpus", "1", "--dump-outputs", str(out)] + SMALL)
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert not {"roofline", "roofline_extra", "cpu_baseline"} & set(d)
+    arrays = {f[:-4]: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))}
+    assert set(arrays) == {"loss", "params", "grads", "bn_running_stats"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["loss"].shape == (1,) and arrays["loss"][0] == np.float32(d["final_loss"])
+    assert arrays["params"].shape == arrays["grads"].shape and arrays["params"].size > 1000
+    assert np.abs(arrays["grads"]).max() > 0
+
+
 @pytest.mark.timeout(120)
 def test_world_size_mismatch_is_refused():
     rc, lines, _ = _run(["--gpus", "1"] + SMALL, {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})

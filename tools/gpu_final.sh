@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 bash tools/gpu_full.sh "$TAG"
 timeout -k 10 300 python -u -c 'import __graft_entry__ as g; g.smoke(); print("SMOKE_OK")' > "$OUT/smoke.log" 2>&1
 tail -1 "$OUT/smoke.log"
-timeout -k 10 600 python -u bench.py > "$OUT/default_bench.json" 2> "$OUT/default_bench.err"
+timeout -k 10 600 python -u bench.py --full > "$OUT/default_bench.json" 2> "$OUT/default_bench.err"
 cat "$OUT/default_bench.json"
 timeout -k 10 300 python -u bench.py --config 4 --cpu-steps 0 --cpu1-steps 0 > "$OUT/c4_bench.json" 2> "$OUT/c4.err"
 timeout -k 10 300 python -u bench.py --config 5 --cpu-steps 0 --cpu1-steps 0 > "$OUT/c5_bench.json" 2> "$OUT/c5.err"

@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-timeout -k 10 300 python -u bench.py --cpu-steps 0 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python -u bench.py --full --cpu-steps 0 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 cat "$OUT/bench.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o prof -- \
   python -u bench.py --steps 20 --warmup 5 --profile "$@" > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err"

@@ -16,7 +16,7 @@ if [ "$MODE" != "notests" ]; then
     > "$OUT/pytest_gpu.log" 2>&1
   tail -3 "$OUT/pytest_gpu.log"
 fi
-timeout -k 10 300 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 300 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cat "$OUT/bench.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o prof -- \
   python -u bench.py --steps 20 --warmup 5 --cpu-steps 0 > "$OUT/prof_bench.json" 2> "$OUT/prof_bench.err"
