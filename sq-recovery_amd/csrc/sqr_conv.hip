@@ -1231,6 +1231,50 @@ static bool direct3w(const sqr_conv_desc* d, const Shape& sh) {
   return !sh.im2col && d->dtype != SQR_DTYPE_F32 && d->R == 3 && d->S == 3 && (d->stride == 1 || d->stride == 2) &&
          d->pad == 1;
 }
+// a direct-kernel call on the descriptor's conv: its forward (x, the KRSC weights -> y) or, with dgrad,
+// its backward-data (dY, the CRSK weights -> dX: the channel counts swapped, the taps flipped)
+static Conv3Call conv3_call(const sqr_conv_desc* d, hipStream_t st, const void* x, const void* w, void* out,
+                            bool dgrad) {
+  Conv3Call c;
+  c.dtype = d->dtype;
+  c.st = st;
+  c.x = x;
+  c.w = w;
+  c.out = out;
+  c.N = d->N;
+  c.H = d->H;
+  c.W = d->W;
+  c.Cin = dgrad ? d->K : d->C;
+  c.Nout = dgrad ? d->C : d->K;
+  c.flip = dgrad ? 1 : 0;
+  c.stride = d->stride;
+  return c;
+}
+// the direct stride-2 backward-data kernel over the four parity classes of the packed CRSK weights
+// (classes of 1, 2, 2 and 4 taps), with an optional addend (compact on the (even, even) pixels if
+// addend_s2); kNotHandled where it does not apply
+static int direct3s2_dgrad(const sqr_conv_desc* d, const Shape& sh, hipStream_t st, const void* dy, const void* w_crsk,
+                           void* dx, const void* addend, int addend_s2) {
+  if (!direct3s2(d, sh)) return kNotHandled;
+  Conv3S2DgradCall c;
+  c.dtype = d->dtype;
+  c.st = st;
+  c.dy = dy;
+  c.w_cls = w_crsk;
+  const int ck = d->C * d->K;
+  c.cls_off[1] = ck;
+  c.cls_off[2] = 3 * ck;
+  c.cls_off[3] = 5 * ck;
+  c.dx = dx;
+  c.N = d->N;
+  c.Ho = sh.Ho;
+  c.Wo = sh.Wo;
+  c.K = d->K;
+  c.C = d->C;
+  c.addend = addend;
+  c.addend_s2 = addend_s2;
+  return conv3s2_dgrad_launch(c);
+}
 
 extern "C" size_t sqr_conv2d_workspace_bytes(const sqr_conv_desc* d, int which) {
   Shape sh;
@@ -1258,13 +1302,9 @@ extern "C" int sqr_conv2d_pack_weight(const float* w_kcrs, const sqr_conv_desc* 
   const int total = d->K * (sh.im2col ? sh.Kp : d->R * d->S * d->C);
   const int blocks = (total + 255) / 256;
   hipStream_t st = as_stream(stream);
-  if (d->dtype != SQR_DTYPE_F32)
-    SQR_DISPATCH16(d->dtype, T,
-                   hipLaunchKernelGGL((pack_weight_kernel<T>), dim3(blocks), dim3(256), 0, st, w_kcrs, d->K, d->C,
-                                      d->R, d->S, d->stride, d->pad, (int)sh.im2col, sh.Kp, (T*)w_krsc, (T*)w_crsk));
-  else
-    hipLaunchKernelGGL((pack_weight_kernel<float>), dim3(blocks), dim3(256), 0, st, w_kcrs, d->K, d->C, d->R,
-                       d->S, d->stride, d->pad, (int)sh.im2col, sh.Kp, (float*)w_krsc, (float*)w_crsk);
+  SQR_DISPATCH_DTYPE(d->dtype, T,
+                     hipLaunchKernelGGL((pack_weight_kernel<T>), dim3(blocks), dim3(256), 0, st, w_kcrs, d->K, d->C,
+                                        d->R, d->S, d->stride, d->pad, (int)sh.im2col, sh.Kp, (T*)w_krsc, (T*)w_crsk));
   SQR_HIP_LAUNCH_CHECK("pack_weight_kernel");
   return 0;
 }
@@ -1294,14 +1334,12 @@ static int conv_fwd_impl(const void* x, const void* w_krsc, void* y, const sqr_c
   a.oph = a.opw = 0;
   a.oH = sh.Ho;
   a.oW = sh.Wo;
-  if (direct3(d, sh)) {
-    rc = conv3_launch(d->dtype, x, w_krsc, y, d->N, d->H, d->W, d->C, d->K, 0, stats, stats_rows, st);
+  if (direct3(d, sh) || direct3s2(d, sh)) {
+    Conv3Call c = conv3_call(d, st, x, w_krsc, y, false);
+    c.stats = stats;
+    c.stats_rows = stats_rows;
+    rc = conv3_launch(c);
     if (rc != kNotHandled) return rc;  // launched (0) or failed; else the shape is not covered
-  }
-  if (direct3s2(d, sh)) {
-    rc = conv3_launch(d->dtype, x, w_krsc, y, d->N, d->H, d->W, d->C, d->K, 0, stats, stats_rows, st, nullptr,
-                      nullptr, 2);
-    if (rc != kNotHandled) return rc;
   }
   a.stats = stats;
   if (stats_rows) {  // one partial row per M tile of the config launch_nt will pick
@@ -1314,8 +1352,7 @@ static int conv_fwd_impl(const void* x, const void* w_krsc, void* y, const sqr_c
       set_error("conv2d_fwd: workspace %zu < %zu", workspace_bytes, need);
       return SQR_E_WORKSPACE;
     }
-    if (d->dtype == SQR_DTYPE_F32) rc = im2col<float>(x, d, sh, workspace, st);
-    else SQR_DISPATCH16(d->dtype, T, rc = im2col<T>(x, d, sh, workspace, st));
+    SQR_DISPATCH_DTYPE(d->dtype, T, rc = im2col<T>(x, d, sh, workspace, st));
     if (rc) return rc;
     a.g = make_gather(workspace, sh.Ho, sh.Wo, sh.Kp, sh.Ho, sh.Wo, 1, 0, 0, 1, 1, 1, d->N, sh.ES);
     a.Kg = sh.Kp;
@@ -1323,8 +1360,7 @@ static int conv_fwd_impl(const void* x, const void* w_krsc, void* y, const sqr_c
     a.g = make_gather(x, d->H, d->W, d->C, sh.Ho, sh.Wo, d->stride, -d->pad, -d->pad, 1, d->R, d->S, d->N, sh.ES);
     a.Kg = d->R * d->S * d->C;
   }
-  if (d->dtype == SQR_DTYPE_F32) return launch_nt<float>(&a, 1, st);
-  SQR_DISPATCH16(d->dtype, T, rc = launch_nt<T>(&a, 1, st));
+  SQR_DISPATCH_DTYPE(d->dtype, T, rc = launch_nt<T>(&a, 1, st));
   return rc;
 }
 
@@ -1358,8 +1394,11 @@ extern "C" int sqr_conv2d_fwd_stats_bnin(const void* x_pre, const float* coef, v
     return SQR_E_UNSUPPORTED;
   }
   const BnInArgs b = {coef, x_act, x_mask};
-  rc = conv3_launch(d->dtype, x_pre, w_krsc, y, d->N, d->H, d->W, d->C, d->K, 0, stats, stats_rows, as_stream(stream),
-                    nullptr, nullptr, 1, nullptr, &b);
+  Conv3Call c = conv3_call(d, as_stream(stream), x_pre, w_krsc, y, false);
+  c.stats = stats;
+  c.stats_rows = stats_rows;
+  c.bnin = &b;
+  rc = conv3_launch(c);
   if (rc == kNotHandled) {
     set_error(x_act ? "conv2d_fwd_stats_bnin: side outputs only on the persistent layer-1 kernel's shapes (64 -> 64 "
                       "channels, 64- or 128-wide maps)"
@@ -1414,24 +1453,19 @@ static int bwd_data_impl(const void* dy, const void* w_crsk, void* dx, const voi
   SQR_CHECK_ARG(addend != dx, "conv2d_bwd_data_acc: addend must not alias dx");
   hipStream_t st = as_stream(stream);
   if (direct3(d, sh)) {
-    rc = conv3_launch(d->dtype, dy, w_crsk, dx, d->N, d->H, d->W, d->K, d->C, 1, nullptr, nullptr, st, addend);
+    Conv3Call c = conv3_call(d, st, dy, w_crsk, dx, true);
+    c.addend = addend;
+    rc = conv3_launch(c);
     if (rc != kNotHandled) return rc;
   }
-  if (d->dtype != SQR_DTYPE_F32 && d->R == 3 && d->S == 3 && d->stride == 2 && d->pad == 1 &&
-      d->H == 2 * sh.Ho && d->W == 2 * sh.Wo) {
-    const int off[4] = {0, d->C * d->K, 3 * d->C * d->K, 5 * d->C * d->K};  // classes of 1, 2, 2, 4 taps
-    rc = conv3s2_dgrad_launch(d->dtype, dy, w_crsk, off, dx, d->N, sh.Ho, sh.Wo, d->K, d->C, st, addend);
-    if (rc != kNotHandled) return rc;
-  }
+  rc = direct3s2_dgrad(d, sh, st, dy, w_crsk, dx, addend, 0);
+  if (rc != kNotHandled) return rc;
   rc = bwd_data_gemm(dy, w_crsk, dx, d, sh, st);
   if (rc || !addend) return rc;
   const long long n = (long long)d->N * d->H * d->W * d->C;
   const unsigned grid = (unsigned)((n + 1023) / 1024);
-  if (d->dtype == SQR_DTYPE_F32)
-    hipLaunchKernelGGL(add_inplace_kernel<float>, dim3(grid), dim3(256), 0, st, (float*)dx, (const float*)addend, n);
-  else
-    SQR_DISPATCH16(d->dtype, T, hipLaunchKernelGGL(add_inplace_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)dx,
-                                                   (const T*)addend, n));
+  SQR_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL(add_inplace_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)dx,
+                                                     (const T*)addend, n));
   SQR_HIP_LAUNCH_CHECK("add_inplace_kernel");
   return 0;
 }
@@ -1469,21 +1503,14 @@ extern "C" int sqr_conv2d_bwd_data_acc_s2(const void* dy, const void* w_crsk, vo
   SQR_CHECK_ARG(d->stride == 2 && d->H == 2 * sh.Ho && d->W == 2 * sh.Wo && !sh.im2col,
                 "conv2d_bwd_data_acc_s2: needs a stride-2 conv with H = 2 Ho, W = 2 Wo");
   hipStream_t st = as_stream(stream);
-  if (d->dtype != SQR_DTYPE_F32 && d->R == 3 && d->S == 3 && d->pad == 1) {
-    const int off[4] = {0, d->C * d->K, 3 * d->C * d->K, 5 * d->C * d->K};
-    rc = conv3s2_dgrad_launch(d->dtype, dy, w_crsk, off, dx, d->N, sh.Ho, sh.Wo, d->K, d->C, st, addend_c, 1);
-    if (rc != kNotHandled) return rc;
-  }
+  rc = direct3s2_dgrad(d, sh, st, dy, w_crsk, dx, addend_c, 1);
+  if (rc != kNotHandled) return rc;
   rc = bwd_data_impl(dy, w_crsk, dx, nullptr, d, stream);
   if (rc) return rc;
   const long long n = (long long)d->N * sh.Ho * sh.Wo * d->C;
   const unsigned grid = (unsigned)((n + 255) / 256);
-  if (d->dtype == SQR_DTYPE_F32)
-    hipLaunchKernelGGL(add_s2_compact_kernel<float>, dim3(grid), dim3(256), 0, st, (float*)dx, (const float*)addend_c,
-                       sh.Ho, sh.Wo, d->C, n);
-  else
-    SQR_DISPATCH16(d->dtype, T, hipLaunchKernelGGL(add_s2_compact_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)dx,
-                                                   (const T*)addend_c, sh.Ho, sh.Wo, d->C, n));
+  SQR_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL(add_s2_compact_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)dx,
+                                                     (const T*)addend_c, sh.Ho, sh.Wo, d->C, n));
   SQR_HIP_LAUNCH_CHECK("add_s2_compact_kernel");
   return 0;
 }
@@ -1507,9 +1534,12 @@ extern "C" int sqr_conv2d_bwd_data_acc_masked(const void* dy, const void* w_crsk
   SQR_CHECK_ARG(dy && w_crsk && dx && addend && addend_mask, "conv2d_bwd_data_acc_masked: null pointer");
   SQR_CHECK_ARG(addend != dx, "conv2d_bwd_data_acc_masked: addend must not alias dx");
   rc = kNotHandled;
-  if (!sh.im2col && direct3(d, sh))
-    rc = conv3_launch(d->dtype, dy, w_crsk, dx, d->N, d->H, d->W, d->K, d->C, 1, nullptr, nullptr, as_stream(stream),
-                      addend, nullptr, 1, addend_mask);
+  if (direct3(d, sh)) {
+    Conv3Call c = conv3_call(d, as_stream(stream), dy, w_crsk, dx, true);
+    c.addend = addend;
+    c.addend_mask = addend_mask;
+    rc = conv3_launch(c);
+  }
   if (rc == kNotHandled) {
     set_error("conv2d_bwd_data_acc_masked: only the direct 3x3 / stride-1 16-bit kernels take a masked addend");
     return SQR_E_UNSUPPORTED;
@@ -1542,8 +1572,11 @@ extern "C" int sqr_conv2d_bwd_data_bn(const void* dy, const void* w_crsk, void* 
   hipStream_t st = as_stream(stream);
   if (direct3(d, sh)) {
     const BnbArgs bnb = {bn_x, relu_mask, bn_mean};
-    rc = conv3_launch(d->dtype, dy, w_crsk, g_out, d->N, d->H, d->W, d->K, d->C, 1, stats, stats_rows, st, nullptr,
-                      &bnb);
+    Conv3Call c = conv3_call(d, st, dy, w_crsk, g_out, true);
+    c.stats = stats;
+    c.stats_rows = stats_rows;
+    c.bnb = &bnb;
+    rc = conv3_launch(c);
     if (rc != kNotHandled) return rc;
   }
   rc = bwd_data_impl(dy, w_crsk, g_out, nullptr, d, stream);
@@ -1573,8 +1606,11 @@ extern "C" int sqr_conv2d_bwd_data_bn_act(const void* dy, const void* w_crsk, vo
   BnbArgs bnb = {bn_x, nullptr, bn_mean};
   bnb.coef = bn_coef;
   bnb.act = act_out;
-  rc = conv3_launch(d->dtype, dy, w_crsk, g_out, d->N, d->H, d->W, d->K, d->C, 1, stats, stats_rows, as_stream(stream),
-                    nullptr, &bnb);
+  Conv3Call c = conv3_call(d, as_stream(stream), dy, w_crsk, g_out, true);
+  c.stats = stats;
+  c.stats_rows = stats_rows;
+  c.bnb = &bnb;
+  rc = conv3_launch(c);
   if (rc == kNotHandled) {
     set_error("conv2d_bwd_data_bn_act: no direct kernel for this shape (sqr_conv2d_bnin_nso_supported)");
     return SQR_E_UNSUPPORTED;
@@ -1614,8 +1650,7 @@ static int bwd_data_gemm(const void* dy, const void* w_crsk, void* dx, const sqr
     }
   }
   if (ncls == 0) return 0;
-  if (d->dtype == SQR_DTYPE_F32) return launch_nt<float>(cl, ncls, st);
-  SQR_DISPATCH16(d->dtype, T, rc = launch_nt<T>(cl, ncls, st));
+  SQR_DISPATCH_DTYPE(d->dtype, T, rc = launch_nt<T>(cl, ncls, st));
   return rc;
 }
 
@@ -1641,8 +1676,7 @@ static int bwd_weight_impl(const void* x, const void* col_in, const void* dy, fl
   if (sh.im2col) {
     const void* col = col_in;
     if (!col) {
-      if (d->dtype == SQR_DTYPE_F32) rc = im2col<float>(x, d, sh, ws, st);
-      else SQR_DISPATCH16(d->dtype, T, rc = im2col<T>(x, d, sh, ws, st));
+      SQR_DISPATCH_DTYPE(d->dtype, T, rc = im2col<T>(x, d, sh, ws, st));
       if (rc) return rc;
       col = ws;
       ws += colb;
@@ -1675,8 +1709,7 @@ static int bwd_weight_impl(const void* x, const void* col_in, const void* dy, fl
     else if (BK % Wo == 0 && Ho % (BK / Wo) == 0) a.rect_wt = Wo;
   }
   const TNPlan p = plan_tn(d->K, Ng, sh.M, sh.ES);
-  if (d->dtype == SQR_DTYPE_F32) rc = launch_tn<float>(a, p, st);
-  else SQR_DISPATCH16(d->dtype, T, rc = launch_tn<T>(a, p, st));
+  SQR_DISPATCH_DTYPE(d->dtype, T, rc = launch_tn<T>(a, p, st));
   if (rc) return rc;
   if (!sh.im2col && d->R == 1 && d->S == 1)  // TN slab [K][C] = KCRS
     return launch_wgrad_sum((const float*)ws, p.splits, (long long)d->K * d->C, dw_kcrs, st, fin, red, red_lds);

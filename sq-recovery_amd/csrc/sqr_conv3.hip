@@ -1762,22 +1762,24 @@ __global__ void __launch_bounds__(256) conv3_wgrad_kernel(D3WArgs a) {
   clock_end(a.tp);
 }
 
+// ---------------------------------------------------------------- launchers
+// Every launcher returns kNotHandled = not applicable (the caller falls back to the implicit-GEMM
+// path), 0 = launched, else an error.  Each kernel family has one table of tiles; a row states the
+// tile's numbers once and carries the launch entries instantiated from them.
 namespace {
-struct D3Cfg {
-  int id, BM, BN, threads, TW, TH, nwb, imgs;
-};
+int g_direct = 1;     // 0 off, 1 on when the grid is big enough, 2 whenever the shape fits
+int g_deep_ring = 1;  // 1: the deep-weight-ring tiles first; 0: their 3-stage twins
 
-int g_direct = 1;  // 0 off, 1 on when the grid is big enough, 2 whenever the shape fits
+// experiment builds (tools/build_exp.sh) read SQR_D3_CFG / SQR_S2F_CFG (a forced tile id) and SQR_EXP
+// (the ablation bits) from the environment; the shipped library sees the default
 #ifdef SQR_EXPERIMENTS
-// experiment builds: SQR_D3_CFG / SQR_S2F_CFG force a candidate id, SQR_EXP sets the ablation bits
-int env_int(const char* n, int dflt) {
+int exp_env(const char* n, int dflt) {
   const char* v = getenv(n);
   return v && *v ? atoi(v) : dflt;
 }
+#else
+constexpr int exp_env(const char*, int dflt) { return dflt; }
 #endif
-int g_persist = 1;  // layer-1 persistent kernel (0: the tiled conv3_kernel; tests compare the two)
-int g_deep_ring = 1;  // 1: the deep-weight-ring tiles (ids 7, 8, 10) first; 0: their 3-stage twins (1, 2, 5)
-
 
 int pow2_log(int x) {
   int l = 0;
@@ -1785,446 +1787,383 @@ int pow2_log(int x) {
   return (1 << l) == x ? l : -1;
 }
 
-// candidate configurations, in order of preference; the first that tiles the shape and gives
-// enough workgroups wins
-bool pick(int N, int H, int W, int Cin, int Nout, D3Cfg* out) {
-  const int nch = Cin / 64;
-  const D3Cfg cands[] = {
-      // id BM   BN  thr  TW  TH nwb imgs
-      {0, 256, 64, 256, 64, 4, 1, 1},    // Nout 64, Cin 64 (layer1; the persistent kernel takes W 64)
-      // deeper weight rings first (bitwise the same results; B=64 fwd: layer2 24.8 vs 25.7 us,
-      // layer3 23.5 vs 23.9, layer4 27.1 vs 28.4 -- scratch/d3_cfg.py)
-      {7, 256, 128, 512, 32, 8, 2, 1},   // W 32 (layer2), 4-stage weight ring
-      {8, 128, 128, 512, 16, 8, 2, 1},   // W 16 (layer3), 6-stage ring
-      {10, 128, 64, 256, 8, 8, 2, 2},    // 8 x 8, two images per tile (layer4), 9-stage ring
-      {1, 256, 128, 512, 32, 8, 2, 1},   // W 32, 3-stage ring
-      {2, 128, 128, 512, 16, 8, 2, 1},   // W 16, 3-stage ring
-      {5, 128, 64, 256, 8, 8, 2, 2},     // 8 x 8, two images per tile (half the weight traffic of id 3)
-      {9, 128, 64, 256, 8, 8, 2, 2},     // id 5 with a 6-stage ring
-      {3, 64, 128, 256, 8, 8, 2, 1},     // W 8 (layer4, odd batch)
-      {4, 256, 64, 256, 16, 16, 2, 1},   // W 16, whole image per tile (slower than id 2 on layer3)
-      {6, 256, 32, 256, 8, 8, 2, 4},     // 8 x 8, four images per tile
-#ifdef SQR_EXPERIMENTS
-      {20, 128, 64, 256, 16, 8, 2, 1},   // W 16 (layer3), 72 KiB: two workgroups per CU
-      {21, 128, 64, 256, 32, 4, 2, 1},   // W 32 (layer2), 80 KiB: two workgroups per CU
-#endif
-  };
-#ifdef SQR_EXPERIMENTS
-  static const int force = env_int("SQR_D3_CFG", -1);
-#else
-  constexpr int force = -1;
-#endif
-  for (const D3Cfg& c : cands) {
-    if (force >= 0 && c.id != force) continue;
-    if (force < 0 && !g_deep_ring && (c.id == 7 || c.id == 8 || c.id == 10)) continue;
-    if (c.id == 0 && !(Nout == 64 && nch == 1)) continue;
-    if (c.id != 0 && Nout % c.BN) continue;
-    if (W % c.TW || H % c.TH) continue;
-    if (c.imgs > 1 && (c.TH != H || c.TW != W || N % c.imgs)) continue;
-    if (c.nwb == 1 && nch != 1) continue;
-    const long long tiles = (long long)(N / c.imgs) * (H / c.TH) * (W / c.TW) * (Nout / c.BN);
-    if (tiles < 128 && g_direct < 2) continue;
-    // measured (scratch/nt_tune.py, B=64): the direct kernel beats the implicit-GEMM one on every
-    // ResNetSQ 3x3/s1 shape: layer2 25.0 vs 28.1 us, layer3 23.6 vs 29.7, layer4 29.1 vs 39.8
-    *out = c;
-    return true;
+// index of a 16-bit dtype's launch entries (SQR_DISPATCH16's rule: everything but f16 is bf16)
+int dt16(int dtype) { return dtype == SQR_DTYPE_F16 ? 1 : 0; }
+
+// ---- conv3_kernel tiles (stride 1 and the stride-2 forward)
+using D3Launch = void (*)(dim3 grid, hipStream_t st, const D3Args& a);
+struct D3Entries {
+  D3Launch plain;  // forward / backward-data
+  D3Launch acc;    // backward-data + addend (stride 1)
+  D3Launch bnb;    // backward-data feeding a BatchNorm backward (stride 1)
+  D3Launch bnin;   // forward with the preceding BatchNorm + ReLU applied on load; null: the tile has none
+};
+struct D3Tile {
+  int id;  // the tile's name: SQR_D3_CFG / SQR_S2F_CFG, DESIGN.md and profiles/ refer to it
+  int BN, WAVES_M, WAVES_N, TW, TH, NWB, IMGS, PD;
+  bool exact_bn;   // takes Nout == BN only
+  bool deep_ring;  // a deep weight ring: skipped when g_deep_ring == 0 (its 3-stage twin follows)
+  // Where the no-side-output path is also the faster one (config-2 step tables, profiles/r06e_c2_steps.txt
+  // against r06a_c2_steps.txt, per BasicBlock): the tiled 32- and 16-wide tiles (ids 7, 8 and their twins)
+  // save the apply pass for +1.2 / +1.3 us on the forward (layers 2 and 3: -4 / -5 us per block).  Not the
+  // persistent layer-1 kernel (its side outputs cost the forward +12 us, the activation store the
+  // backward-data +9.4 us) nor the two-image 8x8 tiles (id 10: the window transform and the loss of the
+  // k20 key cost +7.4 us, more than layer 4's small apply pass).
+  bool nso_faster;
+  D3Entries e[2];  // bf16, f16
+};
+enum : unsigned { kExactBn = 1, kDeepRing = 2, kNsoFaster = 4 };
+// the BNIN column: no apply-on-load instantiation / one with the tile's own ring depth / (> 0) one with
+// this ring depth
+constexpr int kNoBnin = -1, kBninSamePd = 0;
+
+template <typename T, int BN, int WM, int WN, int TW, int TH, int NWB, int IMGS, int PD, bool ACC, bool BNB, int S,
+          bool BNIN>
+void d3_launch(dim3 grid, hipStream_t st, const D3Args& a) {
+  hipLaunchKernelGGL((conv3_kernel<T, IMGS * TH * TW, BN, WM, WN, TW, TH, NWB, IMGS, PD, ACC, BNB, S, BNIN>), grid,
+                     dim3(64 * WM * WN), 0, st, a);
+}
+template <typename T, int BN, int WM, int WN, int TW, int TH, int NWB, int IMGS, int PD, int BNIN_PD, int S>
+constexpr D3Entries d3_entries() {
+  D3Entries e = {d3_launch<T, BN, WM, WN, TW, TH, NWB, IMGS, PD, false, false, S, false>, nullptr, nullptr, nullptr};
+  if constexpr (S == 1) {
+    e.acc = d3_launch<T, BN, WM, WN, TW, TH, NWB, IMGS, PD, true, false, S, false>;
+    e.bnb = d3_launch<T, BN, WM, WN, TW, TH, NWB, IMGS, PD, false, true, S, false>;
   }
-  return false;
+  if constexpr (BNIN_PD != kNoBnin)
+    e.bnin = d3_launch<T, BN, WM, WN, TW, TH, NWB, IMGS, BNIN_PD == kBninSamePd ? PD : BNIN_PD, false, false, S, true>;
+  return e;
+}
+template <int ID, int BN, int WM, int WN, int TW, int TH, int NWB, int IMGS, int PD, int BNIN_PD = kNoBnin, int S = 1>
+constexpr D3Tile d3_tile(unsigned flags = 0) {
+  return {ID, BN, WM, WN, TW, TH, NWB, IMGS, PD, (flags & kExactBn) != 0, (flags & kDeepRing) != 0,
+          (flags & kNsoFaster) != 0,
+          {d3_entries<bf16, BN, WM, WN, TW, TH, NWB, IMGS, PD, BNIN_PD, S>(),
+           d3_entries<f16, BN, WM, WN, TW, TH, NWB, IMGS, PD, BNIN_PD, S>()}};
+}
+
+// Stride-1 tiles in order of preference: the first that tiles the shape and gives enough workgroups
+// wins.  The weight ring has PD + 1 stages.  The apply-on-load instantiations are the first-choice
+// tiles of ResNetSQ's layers 2-4 at 256 / 512 input and their twins (id 7's with the 3-stage ring:
+// the 4-stage one fills the 160 KiB without the coefficient table).
+// Measured (scratch/nt_tune.py, B=64): the direct kernel beats the implicit-GEMM one on every
+// ResNetSQ 3x3/s1 shape: layer2 25.0 vs 28.1 us, layer3 23.6 vs 29.7, layer4 29.1 vs 39.8; the deeper
+// rings (bitwise the same results) B=64 fwd: layer2 24.8 vs 25.7 us, layer3 23.5 vs 23.9, layer4 27.1
+// vs 28.4 (scratch/d3_cfg.py).
+constexpr D3Tile kD3Tiles[] = {
+    //     id   BN WM WN  TW  TH NWB IMGS PD BNIN
+    d3_tile<0, 64, 4, 1, 64, 4, 1, 1, 2>(kExactBn),  // Cin 64 -> Nout 64 (layer1; the persistent kernel takes W 64 / 128)
+    d3_tile<7, 128, 4, 2, 32, 8, 2, 1, 3, 2>(kDeepRing | kNsoFaster),            // W 32 (layer2), 4-stage ring
+    d3_tile<8, 128, 4, 2, 16, 8, 2, 1, 5, kBninSamePd>(kDeepRing | kNsoFaster),  // W 16 (layer3), 6-stage ring
+    d3_tile<10, 64, 2, 2, 8, 8, 2, 2, 8, kBninSamePd>(kDeepRing),  // 8 x 8, two images per tile (layer4), 9-stage ring
+    d3_tile<1, 128, 4, 2, 32, 8, 2, 1, 2, kBninSamePd>(kNsoFaster),  // W 32, 3-stage ring
+    d3_tile<2, 128, 4, 2, 16, 8, 2, 1, 2, kBninSamePd>(kNsoFaster),  // W 16, 3-stage ring
+    d3_tile<5, 64, 2, 2, 8, 8, 2, 2, 2, kBninSamePd>(),  // 8 x 8, two images per tile (half the weight traffic of id 3)
+    d3_tile<3, 128, 2, 2, 8, 8, 2, 1, 2>(),              // W 8 (layer4, odd batch)
+    d3_tile<4, 64, 4, 1, 16, 16, 2, 1, 2>(),             // W 16, whole image per tile (slower than id 2 on layer3)
+};
+// Stride-2 forward tiles (output TH x TW, one image per tile; the four-plane window and the 3-stage
+// weight ring fit 160 KiB): layer 2 (Cin 64: one window), layers 3-4 (Cin 128 / 256: two windows)
+constexpr D3Tile kD3S2FTiles[] = {
+    d3_tile<0, 128, 4, 2, 32, 4, 1, 1, 2, kNoBnin, 2>(),  // Cin 64, Wo 32 (layer 2; 512x512: Wo 64)
+    d3_tile<1, 128, 2, 2, 16, 4, 2, 1, 2, kNoBnin, 2>(),  // Wo 16 (layer 3; 512x512: layer 3 at Wo 32)
+    d3_tile<2, 128, 2, 2, 8, 8, 2, 1, 2, kNoBnin, 2>(),   // Wo 8 (layer 4; 512x512: Wo 16)
+};
+constexpr int kBninMaxC = 512;  // conv3_kernel's BNIN coefficient table
+
+// direct mode 1 leaves grids of fewer than 128 workgroups to the implicit GEMM
+bool enough_tiles(long long tiles) { return !(tiles < 128 && g_direct < 2); }
+
+const D3Tile* pick(int N, int H, int W, int Cin, int Nout) {
+  const int nch = Cin / 64;
+  static const int force = exp_env("SQR_D3_CFG", -1);
+  for (const D3Tile& c : kD3Tiles) {
+    if (force >= 0 && c.id != force) continue;
+    if (force < 0 && !g_deep_ring && c.deep_ring) continue;
+    if (c.exact_bn ? Nout != c.BN : Nout % c.BN) continue;
+    if (W % c.TW || H % c.TH) continue;
+    if (c.IMGS > 1 && (c.TH != H || c.TW != W || N % c.IMGS)) continue;
+    if (c.NWB == 1 && nch != 1) continue;
+    if (!enough_tiles((long long)(N / c.IMGS) * (H / c.TH) * (W / c.TW) * (Nout / c.BN))) continue;
+    return &c;
+  }
+  return nullptr;
+}
+
+const D3Tile* pick_s2f(int N, int Ho, int Wo, int Cin, int Nout) {
+  const int nch = Cin / 64;
+  static const int force = exp_env("SQR_S2F_CFG", -1);
+  for (const D3Tile& c : kD3S2FTiles) {
+    if (force >= 0 && c.id != force) continue;
+    if ((c.NWB == 1) != (nch == 1)) continue;
+    if (Nout % c.BN || Wo % c.TW || Ho % c.TH) continue;
+    if (!enough_tiles((long long)N * (Ho / c.TH) * (Wo / c.TW) * (Nout / c.BN))) continue;
+    return &c;
+  }
+  return nullptr;
+}
+
+// the persistent layer-1 kernel's shapes: 64 -> 64 channels, 64-wide maps in 2-row tiles, 128-wide maps
+// (512x512 input) in 1-row tiles
+int persist_rows(int W) { return W == 64 ? 2 : 1; }  // rows per tile
+bool persist_shape(int Cin, int Nout, int H, int W) {
+  return Cin == 64 && Nout == 64 && (W == 64 || W == 128) && H % persist_rows(W) == 0;
 }
 }  // namespace
+
+int conv3_bnin_nso_ok(int N, int H, int W, int C, int K) {
+  if (g_direct == 0 || C % 64 || K % 64 || pow2_log(W) < 0 || C > kBninMaxC) return 0;
+  if (persist_shape(C, K, H, W)) return 0;
+  // the forward (C -> K, BNIN) and the backward-data (K -> C, BNB with coefficients) both direct
+  const D3Tile* f = pick(N, H, W, C, K);
+  return f && f->nso_faster && pick(N, H, W, K, C) ? 1 : 0;
+}
 
 namespace {
-bool s2_pick(int Ho, int Wo, int K, int C, int* TH, int* TW, int* BN, int* nch) {
-  if (K % 64 || C % 64) return false;
-  *nch = K / 64;
-  *BN = 64;
-  // tile per channel geometry (the launches below are instantiated for these); any image size the
-  // tile divides (256x256 input: layer 2 / 3 / 4 = 32 / 16 / 8 wide, 512x512: 64 / 32 / 16)
-  if (C == 64 && K == 128) {  // layer 2
-    *TH = 8; *TW = 32;
-  } else if (C == 128 && K == 256) {  // layer 3
-    *TH = 4; *TW = 16;
-  } else if (C == 256 && K == 512) {  // layer 4
-    *TH = 8; *TW = 8;
-  } else {
-    return false;
-  }
-  return Wo % *TW == 0 && Ho % *TH == 0;
+// the persistent kernel (measured at B=64, 128 x 128, rocprof-free clock probe: fwd+stats 140 -> 101 us,
+// dgrad 112 -> 91, dgrad+addend 146 -> 116 against the tiled kernel; 64-wide maps in 4-row tiles were
+// slower than 2-row ones: fwd 31.5 vs 30.8 us, dgrad+addend 31.7 vs 29.0)
+template <typename T, int TW, int TH>
+void d3p_launch(const Conv3Call& c, dim3 grid, const D3PArgs& p) {
+  const dim3 blk(256);
+  if (c.bnin)
+    hipLaunchKernelGGL((conv3p_kernel<T, true, false, false, TW, TH, true>), grid, blk, 0, c.st, p);
+  else if (c.bnb)
+    hipLaunchKernelGGL((conv3p_kernel<T, false, false, true, TW, TH>), grid, blk, 0, c.st, p);
+  else if (c.stats)
+    hipLaunchKernelGGL((conv3p_kernel<T, true, false, false, TW, TH>), grid, blk, 0, c.st, p);
+  else if (c.addend)
+    hipLaunchKernelGGL((conv3p_kernel<T, false, true, false, TW, TH>), grid, blk, 0, c.st, p);
+  else
+    hipLaunchKernelGGL((conv3p_kernel<T, false, false, false, TW, TH>), grid, blk, 0, c.st, p);
 }
-}  // namespace
 
-int conv3s2_dgrad_launch(int dtype, const void* dy, const void* w_cls, const int* cls_off, void* dx, int N, int Ho,
-                         int Wo, int K, int C, hipStream_t st, const void* addend, int addend_s2) {
-  if (g_direct == 0) return kNotHandled;
-  int TH, TW, BN, nch;
-  if (!s2_pick(Ho, Wo, K, C, &TH, &TW, &BN, &nch)) return kNotHandled;
-  const size_t dybytes = (size_t)N * Ho * Wo * K * 2, wbytes = (size_t)9 * C * K * 2;
-  if (dybytes >= (1u << 31) || (size_t)N * 4 * Ho * Wo * C * 2 >= (1u << 31)) return kNotHandled;
-  D3S2Args a;
-  a.dy = dy;
-  a.w = w_cls;
-  a.dx = dx;
-  a.addend = addend;
-  a.addend_s2 = addend && addend_s2 ? 1 : 0;
-  a.N = N;
-  a.Ho = Ho;
-  a.Wo = Wo;
-  a.K = K;
-  a.C = C;
-  a.tiles_x = Wo / TW;
-  a.tiles_per_img = (Ho / TH) * a.tiles_x;
-  a.ntn = C / BN;
-  for (int i = 0; i < 4; ++i) a.cls_off[i] = cls_off[i];
-  a.dybytes = (uint32_t)dybytes;
-  a.wbytes = (uint32_t)wbytes;
-  a.tp = probe_clock_take();
-  // measured (N=64, rocprofv3): layer 2 17.9 us (8x32 tile, 5-deep weight ring, 8 waves), layer 3
-  // 17.6 us (4x16 tile, two workgroups per CU), layer 4 20.0 us (one 8x8 image per tile; the
-  // implicit GEMM: 39.6 / 23.2 / 23.7 us); 4x32 / 8x16 / BN 128 / 2x2-wave / deeper-ring variants were
-  // slower
-  const dim3 grid(N * a.tiles_per_img * a.ntn);
-  probe_begin(st);
-#ifdef SQR_EXPERIMENTS
-  static const int xpd = env_int("SQR_S2D_PD", 0);  // experiment builds: another weight-ring depth
-  if (xpd == 2 || xpd == 3 || xpd == 5) {
-    SQR_DISPATCH16(dtype, T, {
-      if (nch == 2) {
-        if (xpd == 2) hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 32, 64, 4, 2, 2, 2>), grid, dim3(512), 0, st, a);
-        else if (xpd == 3) hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 32, 64, 4, 2, 2, 3>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 32, 64, 4, 2, 2, 5>), grid, dim3(512), 0, st, a);
-      } else if (nch == 8) {
-        if (xpd == 2) hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 8, 64, 2, 2, 8, 2>), grid, dim3(256), 0, st, a);
-        else if (xpd == 3) hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 8, 64, 2, 2, 8, 3>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 8, 64, 2, 2, 8, 5>), grid, dim3(256), 0, st, a);
-      } else {
-        if (xpd == 2) hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 4, 16, 64, 2, 2, 4, 2>), grid, dim3(256), 0, st, a);
-        else if (xpd == 3) hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 4, 16, 64, 2, 2, 4, 3>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 4, 16, 64, 2, 2, 4, 5>), grid, dim3(256), 0, st, a);
-      }
-    });
-    probe_end(st);
-    SQR_HIP_LAUNCH_CHECK("conv3s2_dgrad_kernel");
-    return 0;
+int conv3p_launch(const Conv3Call& c, size_t xbytes, size_t wbytes) {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
   }
-#endif
-  SQR_DISPATCH16(dtype, T, {
-    if (nch == 2)
-      hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 32, 64, 4, 2, 2, 5>), grid, dim3(512), 0, st, a);
-    else if (nch == 8)
-      hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 8, 8, 64, 2, 2, 8, 3>), grid, dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, 4, 16, 64, 2, 2, 4, 3>), grid, dim3(256), 0, st, a);
+  // bands: the largest divisor of the per-image tile count giving about one workgroup per CU
+  const int tpi = c.H / persist_rows(c.W);
+  int bpi = 1;
+  for (int d = 1; d <= tpi; ++d)
+    if (tpi % d == 0 && (long long)c.N * d <= ncu) bpi = d;
+  D3PArgs p;
+  p.x = c.x;
+  p.w = c.w;
+  p.out = c.out;
+  p.addend = c.addend;
+  p.addend_mask = c.addend_mask;
+  p.bn_x = c.bnb ? c.bnb->x : nullptr;
+  p.bn_mask = c.bnb ? c.bnb->mask : nullptr;
+  p.bn_mean = c.bnb ? c.bnb->mean : nullptr;
+  p.stats = c.stats;
+  p.in_coef = c.bnin ? c.bnin->coef : nullptr;
+  p.in_act = c.bnin ? c.bnin->act : nullptr;
+  p.in_mask = c.bnin ? c.bnin->mask : nullptr;
+  p.H = c.H;
+  p.bpi = bpi;
+  p.tpb = tpi / bpi;
+  p.flip = c.flip;
+  p.xbytes = (uint32_t)xbytes;
+  p.wbytes = (uint32_t)wbytes;
+  p.tp = probe_clock_take();
+  const dim3 grid(c.N * bpi);
+  if (c.stats_rows) *c.stats_rows = (int)grid.x;  // one partial row per workgroup
+  probe_begin(c.st);
+  SQR_DISPATCH16(c.dtype, T, {
+    if (c.W == 128) d3p_launch<T, 128, 1>(c, grid, p);
+    else d3p_launch<T, 64, 2>(c, grid, p);
   });
-  probe_end(st);
-  SQR_HIP_LAUNCH_CHECK("conv3s2_dgrad_kernel");
+  probe_end(c.st);
+  SQR_HIP_LAUNCH_CHECK("conv3p_kernel");
   return 0;
 }
 
-
-// kNotHandled = not applicable (caller falls back to the implicit-GEMM path), 0 = launched, else error
-// stride-2 forward tiles (output TH x TW, one image per tile; the four-plane window and the 3-stage
-// weight ring fit 160 KiB): layer 2 (Cin 64: one window), layers 3-4 (Cin 128 / 256: two windows)
-namespace {
-struct D3S2FCfg {
-  int id, BM, BN, threads, TW, TH, nwb;
-};
-bool pick_s2f(int N, int Ho, int Wo, int Cin, int Nout, D3S2FCfg* out) {
-  const int nch = Cin / 64;
-  const D3S2FCfg cands[] = {
-      // id BM   BN  thr  TW  TH nwb
-      {0, 128, 128, 512, 32, 4, 1},  // Cin 64, Wo 32 (layer 2; 512x512: Wo 64)
-      {1, 64, 128, 256, 16, 4, 2},   // Wo 16 (layer 3; 512x512: layer 3 at Wo 32)
-      {2, 64, 128, 256, 8, 8, 2},    // Wo 8 (layer 4; 512x512: Wo 16)
-#ifdef SQR_EXPERIMENTS
-      {10, 128, 128, 512, 32, 4, 1},  // id 0 with a 5-stage weight ring (160 KiB)
-      {11, 64, 128, 256, 16, 4, 2},   // id 1, 5-stage ring
-      {12, 64, 128, 256, 8, 8, 2},    // id 2, 5-stage ring
-      {13, 64, 64, 256, 32, 2, 1},    // Cin 64: 2 x 32 output tiles, 68 KiB (two workgroups per CU)
-      {14, 64, 64, 256, 16, 4, 1},    // Cin 64: 4 x 16 output tiles, 64 KiB (two workgroups per CU)
-#endif
-  };
-#ifdef SQR_EXPERIMENTS
-  static const int force = env_int("SQR_S2F_CFG", -1);
-#else
-  constexpr int force = -1;
-#endif
-  for (const D3S2FCfg& c : cands) {
-    if (force >= 0 && c.id != force) continue;
-    if ((c.nwb == 1) != (nch == 1)) continue;
-    if (Nout % c.BN || Wo % c.TW || Ho % c.TH) continue;
-    if ((long long)N * (Ho / c.TH) * (Wo / c.TW) * (Nout / c.BN) < 128 && g_direct < 2) continue;
-    *out = c;
-    return true;
+// the tiled kernel's arguments (Ho, Wo: the output size, = the input's at stride 1)
+D3Args d3_args(const Conv3Call& c, const D3Tile& t, int Ho, int Wo, size_t xbytes, size_t wbytes) {
+  D3Args a = {};
+  a.x = c.x;
+  a.w = c.w;
+  a.out = c.out;
+  a.addend = c.addend;
+  a.addend_mask = c.addend_mask;
+  if (c.bnb) {
+    a.bn_x = c.bnb->x;
+    a.bn_mask = c.bnb->mask;
+    a.bn_mean = c.bnb->mean;
+    a.bn_coef = c.bnb->coef;
+    a.bn_act = c.bnb->act;
   }
-  return false;
-}
-}  // namespace
-
-// tiled configurations with an apply-on-load (BNIN) instantiation
-bool bnin_tiled_id(int id) { return id == 7 || id == 8 || id == 10 || id == 1 || id == 2 || id == 5; }
-constexpr int kBninMaxC = 512;  // conv3_kernel's BNIN coefficient table
-
-// Where the no-side-output path is also the faster one (config-2 step tables, profiles/r06e_c2_steps.txt
-// against r06a_c2_steps.txt, per BasicBlock): the tiled 32- and 16-wide tiles (ids 7, 8) save the
-// apply pass for +1.2 / +1.3 us on the forward (layers 2 and 3: -4 / -5 us per block).  Not the
-// persistent layer-1 kernel (its side outputs cost the forward +12 us, the activation store the
-// backward-data +9.4 us) nor the two-image 8x8 tiles (id 10: the window transform and the loss of the
-// k20 key cost +7.4 us, more than layer 4's small apply pass).
-int conv3_bnin_nso_ok(int N, int H, int W, int C, int K) {
-  if (g_direct == 0 || C % 64 || K % 64 || pow2_log(W) < 0 || C > kBninMaxC) return 0;
-  if (C == 64 && K == 64 && (W == 64 || W == 128) && H % (W == 64 ? 2 : 1) == 0 && g_persist) return 0;
-  D3Cfg f, b;
-  // the forward (C -> K, BNIN) and the backward-data (K -> C, BNB with coefficients) both direct
-  return pick(N, H, W, C, K, &f) && (f.id == 7 || f.id == 8 || f.id == 1 || f.id == 2) && pick(N, H, W, K, C, &b)
-             ? 1
-             : 0;
-}
-
-int conv3_launch(int dtype, const void* x, const void* w, void* out, int N, int H, int W, int Cin, int Nout, int flip,
-                 float* stats, int* stats_rows, hipStream_t st, const void* addend, const BnbArgs* bnb, int stride,
-                 const uint8_t* addend_mask, const BnInArgs* bnin) {
-  if (addend_mask && (!addend || stride != 1)) return kNotHandled;
-  const bool persist_shape = Cin == 64 && Nout == 64 && (W == 64 || W == 128) && H % (W == 64 ? 2 : 1) == 0 && g_persist;
-  if (bnin) {  // apply-on-load: stride-1 forwards with statistics
-    if (stride != 1 || flip || addend || bnb || !stats || (!bnin->act) != (!bnin->mask)) return kNotHandled;
-    // with side outputs (activation + mask): the persistent layer-1 kernel only
-    if (bnin->act && !persist_shape) return kNotHandled;
-  }
-  if (bnb && bnb->act && !bnb->coef) return kNotHandled;  // the activation output needs the coefficients
-  // the mask from the coefficients: the tiled kernels only (layer-1 bn1 keeps the forward's side outputs)
-  if (bnb && bnb->coef && persist_shape) return kNotHandled;
-  if (g_direct == 0) return kNotHandled;
-  if (stride == 2) {  // forward only (H, W: the input size)
-    if (flip || addend || bnb || H % 2 || W % 2 || Cin % 64 || Nout % 64) return kNotHandled;
-    const int Ho = H / 2, Wo = W / 2;
-    D3S2FCfg c;
-    if (!pick_s2f(N, Ho, Wo, Cin, Nout, &c)) return kNotHandled;
-    const size_t xbytes = (size_t)N * H * W * Cin * 2, wbytes = (size_t)Nout * 9 * Cin * 2;
-    if (xbytes >= (1u << 31) || wbytes >= (1u << 31) || (size_t)N * Ho * Wo * Nout * 2 >= (1u << 31)) return kNotHandled;
-    D3Args a = {};
-    a.x = x;
-    a.w = w;
-    a.out = out;
-    a.stats = stats;
-    a.N = N;
-    a.H = Ho;
-    a.W = Wo;
-    a.iH = H;
-    a.iW = W;
-    a.Cin = Cin;
-    a.Nout = Nout;
-    a.tiles_x = Wo / c.TW;
-    a.tiles_per_img = (Ho / c.TH) * a.tiles_x;
-    a.ntm = N * a.tiles_per_img;
-    a.ntn = Nout / c.BN;
-    a.xbytes = (uint32_t)xbytes;
-    a.wbytes = (uint32_t)wbytes;
-    a.tp = probe_clock_take();
-    if (stats_rows) *stats_rows = a.ntm;
-#ifdef SQR_EXPERIMENTS
-    a.exp = env_int("SQR_EXP", 0);
-    if (a.exp & 1) a.stats = nullptr;
-#endif
-    const dim3 grid(a.ntm * a.ntn), blk(c.threads);
-    probe_begin(st);
-    SQR_DISPATCH16(dtype, T, {
-      switch (c.id) {
-        case 0: hipLaunchKernelGGL((conv3_kernel<T, 128, 128, 4, 2, 32, 4, 1, 1, 2, false, false, 2>), grid, blk, 0, st, a); break;
-        case 1: hipLaunchKernelGGL((conv3_kernel<T, 64, 128, 2, 2, 16, 4, 2, 1, 2, false, false, 2>), grid, blk, 0, st, a); break;
-#ifdef SQR_EXPERIMENTS
-        case 10: hipLaunchKernelGGL((conv3_kernel<T, 128, 128, 4, 2, 32, 4, 1, 1, 4, false, false, 2>), grid, blk, 0, st, a); break;
-        case 11: hipLaunchKernelGGL((conv3_kernel<T, 64, 128, 2, 2, 16, 4, 2, 1, 4, false, false, 2>), grid, blk, 0, st, a); break;
-        case 12: hipLaunchKernelGGL((conv3_kernel<T, 64, 128, 2, 2, 8, 8, 2, 1, 4, false, false, 2>), grid, blk, 0, st, a); break;
-        case 13: hipLaunchKernelGGL((conv3_kernel<T, 64, 64, 2, 2, 32, 2, 1, 1, 2, false, false, 2>), grid, blk, 0, st, a); break;
-        case 14: hipLaunchKernelGGL((conv3_kernel<T, 64, 64, 2, 2, 16, 4, 1, 1, 2, false, false, 2>), grid, blk, 0, st, a); break;
-#endif
-        default: hipLaunchKernelGGL((conv3_kernel<T, 64, 128, 2, 2, 8, 8, 2, 1, 2, false, false, 2>), grid, blk, 0, st, a); break;
-      }
-    });
-    probe_end(st);
-    SQR_HIP_LAUNCH_CHECK("conv3_kernel");
-    return 0;
-  }
-  if (Cin % 64 || Nout % 64 || pow2_log(W) < 0) return kNotHandled;
-  const size_t xbytes = (size_t)N * H * W * Cin * 2, wbytes = (size_t)Nout * 9 * Cin * 2;
-  if (xbytes >= (1u << 31) || wbytes >= (1u << 31) || (size_t)N * H * W * Nout * 2 >= (1u << 31)) return kNotHandled;
-  // the persistent kernel: 64-wide maps in 2-row tiles, 128-wide maps (512x512 input) in 1-row tiles
-  // (measured at B=64, 128 x 128, rocprof-free clock probe: fwd+stats 140 -> 101 us, dgrad 112 -> 91,
-  // dgrad+addend 146 -> 116 against the tiled kernel; 64-wide maps in 4-row tiles were slower than
-  // 2-row ones: fwd 31.5 vs 30.8 us, dgrad+addend 31.7 vs 29.0)
-  const int pth = W == 64 ? 2 : 1;  // rows per tile
-  if (Cin == 64 && Nout == 64 && (W == 64 || W == 128) && H % pth == 0 && g_persist) {
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
-    // bands: the largest divisor of the per-image tile count giving about one workgroup per CU
-    const int tpi = H / pth;
-    int bpi = 1;
-    for (int d = 1; d <= tpi; ++d)
-      if (tpi % d == 0 && (long long)N * d <= ncu) bpi = d;
-    D3PArgs p;
-    p.x = x;
-    p.w = w;
-    p.out = out;
-    p.addend = addend;
-    p.addend_mask = addend_mask;
-    p.bn_x = bnb ? bnb->x : nullptr;
-    p.bn_mask = bnb ? bnb->mask : nullptr;
-    p.bn_mean = bnb ? bnb->mean : nullptr;
-    p.stats = stats;
-    p.in_coef = bnin ? bnin->coef : nullptr;
-    p.in_act = bnin ? bnin->act : nullptr;
-    p.in_mask = bnin ? bnin->mask : nullptr;
-    p.H = H;
-    p.bpi = bpi;
-    p.tpb = tpi / bpi;
-    p.flip = flip;
-    p.xbytes = (uint32_t)xbytes;
-    p.wbytes = (uint32_t)wbytes;
-    p.tp = probe_clock_take();
-    const int grid = N * bpi;
-    if (stats_rows) *stats_rows = grid;  // one partial row per workgroup
-    probe_begin(st);
-#define SQR_D3P_LAUNCH(TW_, TH_)                                                                      \
-  if (bnin)                                                                                          \
-    hipLaunchKernelGGL((conv3p_kernel<T, true, false, false, TW_, TH_, true>), dim3(grid), dim3(256), 0, st, p); \
-  else if (bnb)                                                                                      \
-    hipLaunchKernelGGL((conv3p_kernel<T, false, false, true, TW_, TH_>), dim3(grid), dim3(256), 0, st, p); \
-  else if (stats)                                                                                    \
-    hipLaunchKernelGGL((conv3p_kernel<T, true, false, false, TW_, TH_>), dim3(grid), dim3(256), 0, st, p); \
-  else if (addend)                                                                                   \
-    hipLaunchKernelGGL((conv3p_kernel<T, false, true, false, TW_, TH_>), dim3(grid), dim3(256), 0, st, p); \
-  else                                                                                               \
-    hipLaunchKernelGGL((conv3p_kernel<T, false, false, false, TW_, TH_>), dim3(grid), dim3(256), 0, st, p);
-    SQR_DISPATCH16(dtype, T, {
-      if (W == 128) {
-        SQR_D3P_LAUNCH(128, 1)
-      } else {
-        SQR_D3P_LAUNCH(64, 2)
-      }
-    });
-#undef SQR_D3P_LAUNCH
-    probe_end(st);
-    SQR_HIP_LAUNCH_CHECK("conv3p_kernel");
-    return 0;
-  }
-  D3Cfg c;
-  if (!pick(N, H, W, Cin, Nout, &c)) return kNotHandled;
-  if (bnin && (!bnin_tiled_id(c.id) || Cin > kBninMaxC)) return kNotHandled;
-#ifdef SQR_EXPERIMENTS
-#define SQR_D3_EXP_CASES(ACC_, BNB_)                                                                                 \
-    case 20: hipLaunchKernelGGL((conv3_kernel<T, 128, 64, 2, 2, 16, 8, 2, 1, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;   \
-    case 21: hipLaunchKernelGGL((conv3_kernel<T, 128, 64, 2, 2, 32, 4, 2, 1, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;
-#else
-#define SQR_D3_EXP_CASES(ACC_, BNB_)
-#endif
-  D3Args a;
-  a.x = x;
-  a.w = w;
-  a.out = out;
-  a.addend = addend;
-  a.addend_mask = addend_mask;
-  a.bn_x = bnb ? bnb->x : nullptr;
-  a.bn_mask = bnb ? bnb->mask : nullptr;
-  a.bn_mean = bnb ? bnb->mean : nullptr;
-  a.bn_coef = bnb ? bnb->coef : nullptr;
-  a.bn_act = bnb ? bnb->act : nullptr;
-  a.in_coef = bnin ? bnin->coef : nullptr;
-  a.stats = stats;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.iH = H;
-  a.iW = W;
-  a.Cin = Cin;
-  a.Nout = Nout;
-  a.tiles_x = W / c.TW;
-  a.tiles_per_img = (H / c.TH) * a.tiles_x;
-  a.ntm = N / c.imgs * a.tiles_per_img;
-  a.ntn = Nout / c.BN;
-  a.flip = flip;
+  a.in_coef = c.bnin ? c.bnin->coef : nullptr;
+  a.stats = c.stats;
+  a.N = c.N;
+  a.H = Ho;
+  a.W = Wo;
+  a.iH = c.H;
+  a.iW = c.W;
+  a.Cin = c.Cin;
+  a.Nout = c.Nout;
+  a.tiles_x = Wo / t.TW;
+  a.tiles_per_img = (Ho / t.TH) * a.tiles_x;
+  a.ntm = c.N / t.IMGS * a.tiles_per_img;
+  a.ntn = c.Nout / t.BN;
+  a.flip = c.flip;
   a.xbytes = (uint32_t)xbytes;
   a.wbytes = (uint32_t)wbytes;
   a.tp = probe_clock_take();
-  if (stats_rows) *stats_rows = a.ntm;
 #ifdef SQR_EXPERIMENTS
-  a.exp = env_int("SQR_EXP", 0);
+  a.exp = exp_env("SQR_EXP", 0);
   if (a.exp & 1) a.stats = nullptr;
 #endif
-  const dim3 grid(a.ntm * a.ntn), blk(c.threads);
-  probe_begin(st);
-#define SQR_D3_CASES(ACC_, BNB_)                                                                                   \
-  switch (c.id) {                                                                                                  \
-    case 0: hipLaunchKernelGGL((conv3_kernel<T, 256, 64, 4, 1, 64, 4, 1, 1, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;    \
-    case 1: hipLaunchKernelGGL((conv3_kernel<T, 256, 128, 4, 2, 32, 8, 2, 1, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;   \
-    case 2: hipLaunchKernelGGL((conv3_kernel<T, 128, 128, 4, 2, 16, 8, 2, 1, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;   \
-    case 3: hipLaunchKernelGGL((conv3_kernel<T, 64, 128, 2, 2, 8, 8, 2, 1, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;     \
-    case 4: hipLaunchKernelGGL((conv3_kernel<T, 256, 64, 4, 1, 16, 16, 2, 1, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;   \
-    case 5: hipLaunchKernelGGL((conv3_kernel<T, 128, 64, 2, 2, 8, 8, 2, 2, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;     \
-    case 6: hipLaunchKernelGGL((conv3_kernel<T, 256, 32, 4, 1, 8, 8, 2, 4, 2, ACC_, BNB_>), grid, blk, 0, st, a); break;     \
-    case 7: hipLaunchKernelGGL((conv3_kernel<T, 256, 128, 4, 2, 32, 8, 2, 1, 3, ACC_, BNB_>), grid, blk, 0, st, a); break;   \
-    case 8: hipLaunchKernelGGL((conv3_kernel<T, 128, 128, 4, 2, 16, 8, 2, 1, 5, ACC_, BNB_>), grid, blk, 0, st, a); break;   \
-    case 9: hipLaunchKernelGGL((conv3_kernel<T, 128, 64, 2, 2, 8, 8, 2, 2, 5, ACC_, BNB_>), grid, blk, 0, st, a); break;     \
-    SQR_D3_EXP_CASES(ACC_, BNB_)                                                                                   \
-    default: hipLaunchKernelGGL((conv3_kernel<T, 128, 64, 2, 2, 8, 8, 2, 2, 8, ACC_, BNB_>), grid, blk, 0, st, a); break;    \
+  return a;
+}
+}  // namespace
+
+int conv3_launch(const Conv3Call& c) {
+  if (c.addend_mask && (!c.addend || c.stride != 1)) return kNotHandled;
+  const bool persist = persist_shape(c.Cin, c.Nout, c.H, c.W);
+  if (c.bnin) {  // apply-on-load: stride-1 forwards with statistics
+    if (c.stride != 1 || c.flip || c.addend || c.bnb || !c.stats || (!c.bnin->act) != (!c.bnin->mask)) return kNotHandled;
+    // with side outputs (activation + mask): the persistent layer-1 kernel only
+    if (c.bnin->act && !persist) return kNotHandled;
   }
-  SQR_DISPATCH16(dtype, T, {
-    if (bnin) {
-      // apply-on-load instantiations: the first-choice tiles of ResNetSQ's layers 2-4 at 256 / 512 input
-      switch (c.id) {
-        // (id 7's tile with the 3-stage ring: the 4-stage one fills the 160 KiB without the table)
-        case 1:
-        case 7: hipLaunchKernelGGL((conv3_kernel<T, 256, 128, 4, 2, 32, 8, 2, 1, 2, false, false, 1, true>), grid, blk, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((conv3_kernel<T, 128, 128, 4, 2, 16, 8, 2, 1, 2, false, false, 1, true>), grid, blk, 0, st, a); break;
-        case 8: hipLaunchKernelGGL((conv3_kernel<T, 128, 128, 4, 2, 16, 8, 2, 1, 5, false, false, 1, true>), grid, blk, 0, st, a); break;
-        case 5: hipLaunchKernelGGL((conv3_kernel<T, 128, 64, 2, 2, 8, 8, 2, 2, 2, false, false, 1, true>), grid, blk, 0, st, a); break;
-        default: hipLaunchKernelGGL((conv3_kernel<T, 128, 64, 2, 2, 8, 8, 2, 2, 8, false, false, 1, true>), grid, blk, 0, st, a); break;
-      }
-    } else if (bnb) {
-      SQR_D3_CASES(false, true)
-    } else if (addend) {
-      SQR_D3_CASES(true, false)
-    } else {
-      SQR_D3_CASES(false, false)
-    }
-  });
-#undef SQR_D3_CASES
-  probe_end(st);
+  if (c.bnb && c.bnb->act && !c.bnb->coef) return kNotHandled;  // the activation output needs the coefficients
+  // the mask from the coefficients: the tiled kernels only (layer-1 bn1 keeps the forward's side outputs)
+  if (c.bnb && c.bnb->coef && persist) return kNotHandled;
+  if (g_direct == 0 || c.Cin % 64 || c.Nout % 64) return kNotHandled;
+  const bool s2 = c.stride == 2;  // forward only (H, W: the input size)
+  if (s2 ? (c.flip || c.addend || c.bnb || c.H % 2 || c.W % 2) : pow2_log(c.W) < 0) return kNotHandled;
+  const int Ho = s2 ? c.H / 2 : c.H, Wo = s2 ? c.W / 2 : c.W;
+  const size_t xbytes = (size_t)c.N * c.H * c.W * c.Cin * 2, wbytes = (size_t)c.Nout * 9 * c.Cin * 2;
+  if (xbytes >= (1u << 31) || wbytes >= (1u << 31) || (size_t)c.N * Ho * Wo * c.Nout * 2 >= (1u << 31)) return kNotHandled;
+  if (!s2 && persist) return conv3p_launch(c, xbytes, wbytes);
+  const D3Tile* t = s2 ? pick_s2f(c.N, Ho, Wo, c.Cin, c.Nout) : pick(c.N, c.H, c.W, c.Cin, c.Nout);
+  if (!t) return kNotHandled;
+  const D3Entries& e = t->e[dt16(c.dtype)];
+  if (c.bnin && (!e.bnin || c.Cin > kBninMaxC)) return kNotHandled;
+  const D3Args a = d3_args(c, *t, Ho, Wo, xbytes, wbytes);
+  if (c.stats_rows) *c.stats_rows = a.ntm;
+  probe_begin(c.st);
+  (c.bnin ? e.bnin : c.bnb ? e.bnb : c.addend ? e.acc : e.plain)(dim3(a.ntm * a.ntn), c.st, a);
+  probe_end(c.st);
   SQR_HIP_LAUNCH_CHECK("conv3_kernel");
+  return 0;
+}
+
+// ---------------------------------------------------------------- stride-2 backward-data launcher
+namespace {
+using S2DLaunch = void (*)(dim3 grid, hipStream_t st, const D3S2Args& a);
+struct S2DTile {
+  int C, K, TH, TW;  // the layer's channels (dX has C, dY has K) and the tile of dY pixels
+  S2DLaunch e[2];    // bf16, f16
+};
+constexpr int kS2dBN = 64;  // dX channels per workgroup
+template <typename T, int TH, int TW, int WM, int WN, int NCH, int PD>
+void s2d_launch(dim3 grid, hipStream_t st, const D3S2Args& a) {
+  hipLaunchKernelGGL((conv3s2_dgrad_kernel<T, TH, TW, kS2dBN, WM, WN, NCH, PD>), grid, dim3(64 * WM * WN), 0, st, a);
+}
+template <int C, int K, int TH, int TW, int WM, int WN, int PD>
+constexpr S2DTile s2d_tile() {
+  return {C, K, TH, TW, {s2d_launch<bf16, TH, TW, WM, WN, K / 64, PD>, s2d_launch<f16, TH, TW, WM, WN, K / 64, PD>}};
+}
+// One tile per layer geometry, any image size the tile divides (256x256 input: layer 2 / 3 / 4 = 32 /
+// 16 / 8 wide, 512x512: 64 / 32 / 16).  Measured (N=64, rocprofv3): layer 2 17.9 us (8x32 tile, 5-deep
+// weight ring, 8 waves), layer 3 17.6 us (4x16 tile, two workgroups per CU), layer 4 20.0 us (one 8x8
+// image per tile; the implicit GEMM: 39.6 / 23.2 / 23.7 us); 4x32 / 8x16 / BN 128 / 2x2-wave /
+// deeper-ring variants were slower
+constexpr S2DTile kS2DTiles[] = {
+    //        C    K  TH  TW WM WN PD
+    s2d_tile<64, 128, 8, 32, 4, 2, 5>(),   // layer 2
+    s2d_tile<128, 256, 4, 16, 2, 2, 3>(),  // layer 3
+    s2d_tile<256, 512, 8, 8, 2, 2, 3>(),   // layer 4
+};
+const S2DTile* s2_pick(int Ho, int Wo, int K, int C) {
+  for (const S2DTile& t : kS2DTiles)
+    if (t.C == C && t.K == K) return Wo % t.TW == 0 && Ho % t.TH == 0 ? &t : nullptr;
+  return nullptr;
+}
+}  // namespace
+
+int conv3s2_dgrad_launch(const Conv3S2DgradCall& c) {
+  if (g_direct == 0) return kNotHandled;
+  const S2DTile* t = s2_pick(c.Ho, c.Wo, c.K, c.C);
+  if (!t) return kNotHandled;
+  const size_t dybytes = (size_t)c.N * c.Ho * c.Wo * c.K * 2, wbytes = (size_t)9 * c.C * c.K * 2;
+  if (dybytes >= (1u << 31) || (size_t)c.N * 4 * c.Ho * c.Wo * c.C * 2 >= (1u << 31)) return kNotHandled;
+  D3S2Args a;
+  a.dy = c.dy;
+  a.w = c.w_cls;
+  a.dx = c.dx;
+  a.addend = c.addend;
+  a.addend_s2 = c.addend && c.addend_s2 ? 1 : 0;
+  a.N = c.N;
+  a.Ho = c.Ho;
+  a.Wo = c.Wo;
+  a.K = c.K;
+  a.C = c.C;
+  a.tiles_x = c.Wo / t->TW;
+  a.tiles_per_img = (c.Ho / t->TH) * a.tiles_x;
+  a.ntn = c.C / kS2dBN;
+  for (int i = 0; i < 4; ++i) a.cls_off[i] = c.cls_off[i];
+  a.dybytes = (uint32_t)dybytes;
+  a.wbytes = (uint32_t)wbytes;
+  a.tp = probe_clock_take();
+  probe_begin(c.st);
+  t->e[dt16(c.dtype)](dim3(c.N * a.tiles_per_img * a.ntn), c.st, a);
+  probe_end(c.st);
+  SQR_HIP_LAUNCH_CHECK("conv3s2_dgrad_kernel");
   return 0;
 }
 
 // ---------------------------------------------------------------- weight-gradient launcher
 namespace {
+using D3WLaunch = void (*)(dim3 grid, hipStream_t st, const D3WArgs& a);
+struct D3WTile {
+  int stride, TW, TH;  // a chunk of TH x TW output pixels
+  D3WLaunch e[2];      // bf16, f16
+};
+template <typename T, int S, int TW, int TH, int STAGES>
+void d3w_launch(dim3 grid, hipStream_t st, const D3WArgs& a) {
+  hipLaunchKernelGGL((conv3_wgrad_kernel<T, TW, TH, STAGES, S>), grid, dim3(256), 0, st, a);
+}
+template <int S, int TW, int TH, int STAGES>
+constexpr D3WTile d3w_tile() {
+  return {S, TW, TH, {d3w_launch<bf16, S, TW, TH, STAGES>, d3w_launch<f16, S, TW, TH, STAGES>}};
+}
+// Per stride, widest first: a map takes the first tile that is not wider than it.
+// stride 1: chunks of 128 pixels (64 for W = 8), a taller window amortising its halo rows;
+// stride 2: 64-pixel chunks (the four-plane window of a 128-pixel chunk would not fit 3 stages)
+constexpr D3WTile kD3WTiles[] = {
+    //  stride TW TH STAGES
+    d3w_tile<1, 64, 2, 3>(), d3w_tile<1, 32, 4, 3>(), d3w_tile<1, 16, 8, 3>(), d3w_tile<1, 8, 8, 4>(),
+    d3w_tile<2, 32, 2, 3>(), d3w_tile<2, 16, 4, 3>(), d3w_tile<2, 8, 8, 3>(),
+};
+
 struct D3WPlan {
-  int TW, TH, splits, cps, nchunks, chunks_per_img, tiles_x, ntiles, Ho, Wo;
+  const D3WTile* tile;
+  int splits, cps, nchunks, chunks_per_img, tiles_x, ntiles, Ho, Wo;
 };
 bool plan_w(int N, int H, int W, int C, int K, int stride, D3WPlan* p) {
   if (g_direct == 0 || C % 64 || K % 64 || (stride != 1 && stride != 2)) return false;
   if (stride == 2 && (H % 2 || W % 2)) return false;
   const int Ho = H / stride, Wo = W / stride;
   if (Wo < 8 || pow2_log(Wo) < 0) return false;
-  // stride 1: chunks of 128 pixels (64 for W = 8), a taller window amortising its halo rows;
-  // stride 2: 64-pixel chunks (the four-plane window of a 128-pixel chunk would not fit 3 stages)
-  int TW, TH;
-  if (stride == 1) {
-    TW = Wo >= 64 ? 64 : Wo;
-    TH = TW == 8 ? 8 : 128 / TW;
-  } else {
-    TW = Wo >= 32 ? 32 : Wo;
-    TH = 64 / TW;
-  }
-  if (Ho % TH) return false;
+  const D3WTile* t = nullptr;
+  for (const D3WTile& c : kD3WTiles)
+    if (c.stride == stride && c.TW <= Wo) {
+      t = &c;
+      break;
+    }
+  if (!t || Ho % t->TH) return false;
   if ((size_t)N * H * W * C * 2 >= (1u << 31) || (size_t)N * Ho * Wo * K * 2 >= (1u << 31)) return false;
-  p->TW = TW;
-  p->TH = TH;
+  p->tile = t;
   p->Ho = Ho;
   p->Wo = Wo;
-  p->tiles_x = Wo / TW;
-  p->chunks_per_img = (Ho / TH) * p->tiles_x;
+  p->tiles_x = Wo / t->TW;
+  p->chunks_per_img = (Ho / t->TH) * p->tiles_x;
   p->nchunks = N * p->chunks_per_img;
   p->ntiles = (K / 64) * (C / 64);
   int splits = (256 + p->ntiles - 1) / p->ntiles;  // one workgroup per CU
@@ -2267,24 +2206,8 @@ int conv3w_launch(int dtype, const void* x, const void* dy, float* slab, size_t 
   a.dybytes = (uint32_t)((size_t)N * p.Ho * p.Wo * K * 2);
   a.tp = probe_clock_take();
   *splits = p.splits;
-  const dim3 grid(p.splits * p.ntiles), blk(256);
   probe_begin(st);
-  SQR_DISPATCH16(dtype, T, {
-    if (stride == 1) {
-      switch (p.TW) {
-        case 64: hipLaunchKernelGGL((conv3_wgrad_kernel<T, 64, 2, 3, 1>), grid, blk, 0, st, a); break;
-        case 32: hipLaunchKernelGGL((conv3_wgrad_kernel<T, 32, 4, 3, 1>), grid, blk, 0, st, a); break;
-        case 16: hipLaunchKernelGGL((conv3_wgrad_kernel<T, 16, 8, 3, 1>), grid, blk, 0, st, a); break;
-        default: hipLaunchKernelGGL((conv3_wgrad_kernel<T, 8, 8, 4, 1>), grid, blk, 0, st, a); break;
-      }
-    } else {
-      switch (p.TW) {
-        case 32: hipLaunchKernelGGL((conv3_wgrad_kernel<T, 32, 2, 3, 2>), grid, blk, 0, st, a); break;
-        case 16: hipLaunchKernelGGL((conv3_wgrad_kernel<T, 16, 4, 3, 2>), grid, blk, 0, st, a); break;
-        default: hipLaunchKernelGGL((conv3_wgrad_kernel<T, 8, 8, 3, 2>), grid, blk, 0, st, a); break;
-      }
-    }
-  });
+  p.tile->e[dt16(dtype)](dim3(p.splits * p.ntiles), st, a);
   probe_end(st);
   SQR_HIP_LAUNCH_CHECK("conv3_wgrad_kernel");
   return 0;

@@ -63,6 +63,16 @@ template <typename T> __device__ __forceinline__ float hi2f(uint32_t p) {
       __VA_ARGS__;                          \
     }                                       \
   } while (0)
+// the same over all three descriptor dtypes
+#define SQR_DISPATCH_DTYPE(dtype, T, ...)    \
+  do {                                       \
+    if ((dtype) == SQR_DTYPE_F32) {          \
+      typedef float T;                       \
+      __VA_ARGS__;                           \
+    } else {                                 \
+      SQR_DISPATCH16(dtype, T, __VA_ARGS__); \
+    }                                        \
+  } while (0)
 
 // clock probe (sqr_probe_arm_clock): first workgroup start / last workgroup end, stores drained
 __device__ __forceinline__ void clock_begin(unsigned long long* tp) {
@@ -150,8 +160,6 @@ __device__ __forceinline__ int tn_swz(int row, int win) {
 // from every hipError_t and SQR_E_* code)
 constexpr int kNotHandled = -1000;
 
-// direct 3x3/s1/p1 bf16 / fp16 kernel (sqr_conv3.hip): kNotHandled = shape not handled (use the
-// implicit-GEMM path), 0 = launched, otherwise an error code
 // the following BatchNorm's operands for a backward-data launch that feeds its backward (BNB):
 // the stored value becomes dgrad * mask and stats receives (sum g, sum g*(x - mean)) partial rows
 struct BnbArgs {
@@ -161,11 +169,6 @@ struct BnbArgs {
   const float* coef = nullptr;  // non-null: the mask is recomputed from x and the forward [2][C] (scale, shift)
   void* act = nullptr;          // non-null (with coef): the activation relu(x * scale + shift) is written too
 };
-// addend (nullable, backward-data only): out = conv + addend, fused into the epilogue;
-// bnb (nullable, backward-data only): see BnbArgs (stats / stats_rows then receive its partials)
-// stride 2 (forward only, flip 0, no addend / bnb): H, W are the input size
-// addend_mask (nullable, with addend, stride 1): the addend is added only where its bit is set (a
-// ReLU-masked gradient read as (dy, mask) instead of a materialised copy)
 // the preceding BatchNorm + ReLU applied on load (stride-1 forwards with stats): x is that BatchNorm's
 // input, coef its [2][Cin] (scale, shift); act / mask (the persistent layer-1 kernel only) receive the
 // activation and its ReLU mask as side outputs, or are both null (no side outputs: the backward-data
@@ -175,20 +178,47 @@ struct BnInArgs {
   void* act;
   uint8_t* mask;
 };
-int conv3_launch(int dtype, const void* x, const void* w, void* out, int N, int H, int W, int Cin, int Nout, int flip,
-                 float* stats, int* stats_rows, hipStream_t st, const void* addend = nullptr,
-                 const BnbArgs* bnb = nullptr, int stride = 1, const uint8_t* addend_mask = nullptr,
-                 const BnInArgs* bnin = nullptr);
+// direct 3x3/p1 bf16 / fp16 kernel (sqr_conv3.hip): kNotHandled = shape not handled (use the
+// implicit-GEMM path), 0 = launched, otherwise an error code
+struct Conv3Call {
+  int dtype = 0;
+  hipStream_t st = nullptr;
+  const void* x = nullptr;  // [N][H][W][Cin]
+  const void* w = nullptr;  // [Nout][9][Cin]
+  void* out = nullptr;
+  int N = 0, H = 0, W = 0, Cin = 0, Nout = 0;
+  int flip = 0;    // 1: the taps flipped (backward-data: x = dY, w = the CRSK weights, out = dX)
+  int stride = 1;  // 2: forward only (flip 0, no addend / bnb); H, W are the input size
+  float* stats = nullptr;     // BatchNorm partials of the output (bnb: of its backward) and ...
+  int* stats_rows = nullptr;  // ... the number of partial rows written
+  const void* addend = nullptr;  // backward-data only: out = conv + addend, fused into the epilogue
+  // with addend, stride 1: the addend is added only where its bit is set (a ReLU-masked gradient read as
+  // (dy, mask) instead of a materialised copy)
+  const uint8_t* addend_mask = nullptr;
+  const BnbArgs* bnb = nullptr;    // backward-data only
+  const BnInArgs* bnin = nullptr;  // stride-1 forwards with stats
+};
+int conv3_launch(const Conv3Call& c);
 // 1 if a bn1 -> ReLU -> conv (C -> K, 3x3 / s1 / p1, 16-bit) runs entirely on direct kernels without the
 // activation in memory: the forward applies on load without side outputs and the backward-data (K -> C)
 // recomputes the mask and writes the activation (BnbArgs::coef / act)
 int conv3_bnin_nso_ok(int N, int H, int W, int C, int K);
 // direct 3x3/stride-2/pad-1 bf16 backward-data over the four output-parity classes (w_cls = the
 // packed parity-class weights of sqr_conv2d_pack_weight, cls_off in elements): kNotHandled = not handled
-// addend_s2 (with addend): the addend is compact [N][Ho][Wo][C] and lands on the (even, even) dX
-// pixels only (a stride-2 1x1 downsample conv's input gradient)
-int conv3s2_dgrad_launch(int dtype, const void* dy, const void* w_cls, const int* cls_off, void* dx, int N, int Ho,
-                         int Wo, int K, int C, hipStream_t st, const void* addend = nullptr, int addend_s2 = 0);
+struct Conv3S2DgradCall {
+  int dtype = 0;
+  hipStream_t st = nullptr;
+  const void* dy = nullptr;
+  const void* w_cls = nullptr;
+  int cls_off[4] = {0, 0, 0, 0};
+  void* dx = nullptr;
+  int N = 0, Ho = 0, Wo = 0, K = 0, C = 0;
+  const void* addend = nullptr;  // dx = dgrad + addend
+  // with addend: the addend is compact [N][Ho][Wo][C] and lands on the (even, even) dX pixels only (a
+  // stride-2 1x1 downsample conv's input gradient)
+  int addend_s2 = 0;
+};
+int conv3s2_dgrad_launch(const Conv3S2DgradCall& c);
 // direct 3x3 / pad-1 / stride 1 or 2 bf16 weight gradient: fp32 slabs [splits][K][C][3][3] (torch's
 // KCRS order: the gradient is their elementwise sum, wgrad_sum_kernel).  conv3w_slab_bytes = 0 if
 // not handled.  H, W: the input's size.

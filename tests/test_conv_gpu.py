@@ -127,20 +127,21 @@ def test_conv_deterministic():
         assert torch.equal(a, b)
 
 
-# direct 3x3/s1/p1 kernel (sqr_conv3.hip): one shape per tile configuration (and multi-tile rows,
-# Cin != Nout); forced on (mode 2) so the small test batches take it, and compared with the
-# implicit-GEMM path (mode 0) and the float64 reference
+# direct 3x3/s1/p1 kernel (sqr_conv3.hip): the persistent kernel and the first-choice tiles (and
+# multi-tile rows, Cin != Nout); forced on (mode 2) so the small test batches take it, and compared
+# with the implicit-GEMM path (mode 0) and the float64 reference.  Tile ids: sqr_conv3.hip kD3Tiles
+# (test_conv3_tile_entries and test_conv3_ring_twins reach the other tiles and entries)
 DIRECT = [
     (2, 64, 64, 64),     # layer-1 persistent kernel (resident weights), one tile per workgroup
     (20, 64, 64, 64),    # persistent, several tiles per workgroup (640 tiles > CUs)
-    (1, 64, 128, 64),    # cfg 0, two tiles per image row
-    (2, 128, 32, 128),   # cfg 1 (TW 32 x TH 8, double-buffered window, 2 chunks)
-    (1, 128, 64, 128),   # cfg 1, two tiles per row
-    (2, 256, 16, 256),   # cfg 2 (TW 16 x TH 8)
-    (2, 512, 8, 512),    # cfg 5 (two 8 x 8 images per tile, 8 chunks)
-    (3, 512, 8, 512),    # cfg 3 (odd batch: one image per tile)
-    (2, 128, 16, 256),   # Cin != Nout
-    (2, 64, 32, 128),    # fwd direct (cfg 1, one chunk); dgrad falls back
+    (1, 64, 128, 64),    # persistent, 128-wide maps in 1-row tiles
+    (2, 128, 32, 128),   # tile 7 (TW 32 x TH 8, double-buffered window, 2 chunks)
+    (1, 128, 64, 128),   # tile 7, two tiles per row
+    (2, 256, 16, 256),   # tile 8 (TW 16 x TH 8)
+    (2, 512, 8, 512),    # tile 10 (two 8 x 8 images per tile, 8 chunks)
+    (3, 512, 8, 512),    # tile 3 (odd batch: one image per tile)
+    (2, 128, 16, 256),   # tile 8, Cin != Nout
+    (2, 64, 32, 128),    # fwd tile 7 (one chunk); dgrad (128 -> 64) tile 4
 ]
 
 
@@ -179,6 +180,120 @@ def test_conv3_direct(shape, dtype):
     assert _rel(res[2][0], res[0][0]) <= 8e-3
     assert _rel(res[2][1], res[0][1]) <= 8e-3
     assert _rel(res[2][3], res[0][3]) <= 2e-4
+
+
+def _cl(t, dtype):
+    return t.to(DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+
+
+def _entry_operands(N, C, H, W, K, dtype, seed):
+    """CPU operands (rounded to dtype, as float32) of one 3x3 / s1 / p1 conv and of the entries that
+    ride on its backward-data: the addend, and the following BatchNorm's input, ReLU mask and mean."""
+    g = torch.Generator().manual_seed(seed)
+    o = {"x": torch.randn(N, C, H, W, generator=g).to(dtype).float(),
+         "w": torch.randn(K, C, 3, 3, generator=g) / (C * 9) ** 0.5,
+         "gy": torch.randn(N, K, H, W, generator=g).to(dtype).float(),
+         "add": torch.randn(N, C, H, W, generator=g).to(dtype).float(),
+         "bn_x": (torch.randn(N, C, H, W, generator=g) * 1.5 + 0.3).to(dtype).float(),
+         "keep": torch.rand(N, C, H, W, generator=g) > 0.4,
+         "mean": torch.randn(C, generator=g) * 0.2}
+    # 1-bit mask in the NHWC element order, 8 channels per byte (bit i = channel 8v + i)
+    bits = o["keep"].permute(0, 2, 3, 1).reshape(-1, 8).to(torch.int64)
+    o["mask"] = (bits << torch.arange(8)).sum(1).to(torch.uint8)
+    return o
+
+
+# The tiles the shapes above do not reach, and every entry of theirs (forward + statistics, plain
+# backward-data, + addend, + BatchNorm-backward epilogue), at the smallest shape that selects the tile in
+# both directions (direct mode 2): tile 0 (64 -> 64 on a 256-wide map: 64- and 128-wide ones go to the
+# persistent kernel), tile 3 (one 8 x 8 image per tile, odd batch), tile 4 (a whole 16 x 16 image per tile)
+TILE_ENTRIES = [(1, 64, 4, 256, 64), (1, 128, 8, 8, 128), (1, 64, 16, 16, 64)]
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("shape", TILE_ENTRIES, ids=lambda s: "N%dC%dH%dW%dK%d" % s)
+def test_conv3_tile_entries(shape, dtype):
+    from sqr import conv as sc
+    from sqr._lib import lib
+    N, C, H, W, K = shape
+    o = _entry_operands(N, C, H, W, K, dtype, N + C + H + W + K)
+    yr, dxr, dwr = _f64_fwd_dgrad_wgrad(o["x"], o["w"].to(dtype).float(), o["gy"], 1, 1)
+    d = sc._desc(N, C, H, W, K, 3, 3, 1, 1, dtype)
+    krsc, crsk = sc.pack_weight(o["w"].to(DEV), d, True)
+    xg, gyg = _cl(o["x"], dtype), _cl(o["gy"], dtype)
+    old = lib().sqr_conv_set_direct(2)
+    try:
+        y, st = sc.conv2d_fwd(xg, krsc, d, stats=True)
+        dx = sc.conv2d_bwd_data(gyg, crsk, d)
+        acc = sc.conv2d_bwd_data_acc(gyg, crsk, d, _cl(o["add"], dtype))
+        gg, bst = sc.conv2d_bwd_data_bn(gyg, crsk, d, _cl(o["bn_x"], dtype), o["mask"].to(DEV), o["mean"].to(DEV))
+        dw = sc.conv2d_bwd_weight(xg, gyg, d)
+        torch.cuda.synchronize()
+    finally:
+        lib().sqr_conv_set_direct(old)
+    tol = 8e-3 if dtype == torch.bfloat16 else 1e-3
+    assert _rel(y, yr) <= tol
+    assert _rel(dx, dxr) <= tol
+    assert _rel(dw, dwr) <= 2e-4
+    assert _rel(acc, dxr + o["add"].double()) <= tol
+    assert _rel(gg, dxr * o["keep"]) <= tol
+    yd = y.double().cpu()
+    tot = _totals(st)
+    assert _rel(tot[0], yd.sum((0, 2, 3))) <= 1e-5
+    assert _rel(tot[1], (yd * yd).sum((0, 2, 3))) <= 1e-5
+    # the BatchNorm-backward sums are those of the stored g
+    gd = gg.double().cpu()
+    btot = bst.double().sum(0).cpu()
+    assert bst.shape[1:] == (2, C)
+    assert _rel(btot[0], gd.sum((0, 2, 3))) <= 1e-5
+    assert _rel(btot[1], (gd * (o["bn_x"].double() - o["mean"].double().view(1, C, 1, 1))).sum((0, 2, 3))) <= 1e-5
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("shape", [(2, 128, 32, 128), (2, 256, 16, 256), (2, 512, 8, 512)],
+                         ids=lambda s: "N%dC%dH%dK%d" % s)
+def test_conv3_ring_twins(shape, dtype):
+    """The deep-weight-ring tiles (7, 8, 10) and their 3-stage twins (1, 2, 5; sqr_conv_set_deep_ring(0))
+    on every entry: forward + statistics, apply-on-load forward without side outputs, plain
+    backward-data, + addend, + BatchNorm-backward epilogue.  The ring depth changes how far ahead weight
+    tiles are fetched, not the accumulation order: every output and the statistics bitwise equal.  The
+    twins' forward and backward-data also against float64."""
+    from sqr import conv as sc
+    from sqr._lib import lib
+    N, C, H, K = shape
+    o = _entry_operands(N, C, H, H, K, dtype, 3 * N + C + H + K)
+    g = torch.Generator().manual_seed(C + H)
+    coef = torch.cat([torch.randn(C, generator=g) * 0.8, torch.randn(C, generator=g) * 0.5]).to(DEV)
+    d = sc._desc(N, C, H, H, K, 3, 3, 1, 1, dtype)
+    krsc, crsk = sc.pack_weight(o["w"].to(DEV), d, True)
+    xg, gyg = _cl(o["x"], dtype), _cl(o["gy"], dtype)
+    addg, bxg = _cl(o["add"], dtype), _cl(o["bn_x"], dtype)
+    res = {}
+    L = lib()
+    old_direct = L.sqr_conv_set_direct(2)
+    old_ring = L.sqr_conv_set_deep_ring(1)
+    try:
+        for ring in (1, 0):
+            L.sqr_conv_set_deep_ring(ring)
+            y, st = sc.conv2d_fwd(xg, krsc, d, stats=True)
+            bnin = sc.conv2d_fwd_bnin(xg, coef, None, None, krsc, d)
+            assert bnin is not None
+            dx = sc.conv2d_bwd_data(gyg, crsk, d)
+            acc = sc.conv2d_bwd_data_acc(gyg, crsk, d, addg)
+            gg, bst = sc.conv2d_bwd_data_bn(gyg, crsk, d, bxg, o["mask"].to(DEV), o["mean"].to(DEV))
+            torch.cuda.synchronize()
+            res[ring] = {"y": y, "stats": st, "bnin_y": bnin[0], "bnin_stats": bnin[1], "dx": dx, "acc": acc,
+                         "bnb_g": gg, "bnb_stats": bst}
+    finally:
+        L.sqr_conv_set_deep_ring(old_ring)
+        L.sqr_conv_set_direct(old_direct)
+    for name in res[1]:
+        assert res[1][name].shape == res[0][name].shape, name
+        assert torch.equal(res[1][name], res[0][name]), name
+    yr, dxr, _ = _f64_fwd_dgrad_wgrad(o["x"], o["w"].to(dtype).float(), o["gy"], 1, 1)
+    tol = 8e-3 if dtype == torch.bfloat16 else 1e-3
+    assert _rel(res[0]["y"], yr) <= tol
+    assert _rel(res[0]["dx"], dxr) <= tol
 
 
 @pytest.mark.parametrize("N,H", [(64, 64), (48, 64), (128, 64), (64, 128), (48, 128), (16, 128)])

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Experiment variant of libsqr (never the shipped library): sqr_conv3.hip rebuilt with
-# -DSQR_EXPERIMENTS (forced tile configurations SQR_D3_CFG / SQR_S2F_CFG, ablation bits SQR_EXP) and,
-# with "stamps" as the first argument, the per-workgroup SQR_STAMPS timeline too.  Linked with the
-# regular objects (make first).  Output: tools/exp_lib/libsqr.so or tools/exp_stamps_lib/libsqr.so
+# -DSQR_EXPERIMENTS (SQR_D3_CFG / SQR_S2F_CFG force a row of the shipped tile tables kD3Tiles /
+# kD3S2FTiles by its id, SQR_EXP sets the ablation bits) and, with "stamps" as the first argument, the
+# per-workgroup SQR_STAMPS timeline too.  A new candidate tile is one more row in its table.  Linked with
+# the regular objects (make first).  Output: tools/exp_lib/libsqr.so or tools/exp_stamps_lib/libsqr.so
 set -euo pipefail
 cd "$(dirname "$0")/.."
 make -C sq-recovery_amd/csrc -j8 >/dev/null
