@@ -424,7 +424,9 @@ int sqr_stem_fused_bwd(const void* x, int x_dtype, int y_dtype, int N, int H, in
  * (and w_crsk when set; K, C multiples of 64).  step: the parameter's device step counter (float),
  * read as t = step + 1 for the bias corrections and incremented.  grad_scale multiplies every
  * gradient as it is read (1 = torch.optim.Adam; 1/N averages gradients all-reduced with SUM over N
- * data-parallel ranks).  params is a host array. */
+ * data-parallel ranks).  params is a host array.  One call writes w_crsk for at most 24 convs and
+ * packs rows of C * R * S <= 16384 floats, stride <= 2; every argument of the call is checked before
+ * the first launch, so a call that returns non-zero has changed nothing. */
 typedef struct sqr_adam_param {
   float* p;
   const float* g;

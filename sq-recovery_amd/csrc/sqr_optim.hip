@@ -236,6 +236,9 @@ __global__ void __launch_bounds__(256) adam_kernel(Jobs J) {
   }
 }
 
+constexpr int MAXP = 80;   // parameters per call (CJobs::steps)
+constexpr int MAXCJ = 24;  // dgrad-packing convs per call (CJobs::j)
+
 struct CJob {
   const uint16_t* krsc;  // [K][RS][C] (bf16 or fp16 bits)
   uint16_t* crsk;        // parity classes [C][Rc][Sc][K] back to back
@@ -244,10 +247,10 @@ struct CJob {
   int ntk, ntc;      // 64-wide tiles of K and C
 };
 struct CJobs {
-  CJob j[24];
-  int start[25];
+  CJob j[MAXCJ];
+  int start[MAXCJ + 1];
   int njobs;
-  float* steps[80];  // step counters to increment (block 0)
+  float* steps[MAXP];  // step counters to increment (block 0)
   int nsteps;
   const int* found_inf;  // nullable: != 0 -> the step was skipped (counters stay)
 };
@@ -322,10 +325,35 @@ __global__ void __launch_bounds__(256) crsk_kernel(CJobs J) {
 using namespace sqr;
 using namespace sqr::optim;
 
+// Every argument check of sqr_adam_step_amp, over the whole call and before its first launch: a
+// rejected call leaves every parameter, moment, counter and packed buffer as it was (a check made
+// inside the launch loop would find a bad parameter 41 only after the first 40 had been updated).
+static int check_adam_params(const sqr_adam_param* params, int nparams) {
+  SQR_CHECK_ARG(params && nparams >= 0 && nparams <= MAXP, "adam_step: 0 <= nparams <= %d", MAXP);
+  int ncj = 0;
+  for (int i = 0; i < nparams; ++i) {
+    const sqr_adam_param& q = params[i];
+    SQR_CHECK_ARG(q.p && q.g && q.exp_avg && q.exp_avg_sq && q.step && q.n > 0 && q.n < (1ll << 31),
+                  "adam_step: parameter %d: null pointer or bad size", i);
+    if (!q.w_krsc) continue;
+    const sqr_conv_desc& d = q.desc;
+    SQR_CHECK_ARG((d.dtype == SQR_DTYPE_BF16 || d.dtype == SQR_DTYPE_F16) &&
+                      (long long)d.K * d.C * d.R * d.S == q.n && d.stride >= 1 && d.stride <= 2,
+                  "adam_step: parameter %d: packing needs a bf16 / fp16 descriptor matching the weight", i);
+    SQR_CHECK_ARG((size_t)d.C * d.R * d.S * 4 <= 64 * 1024,
+                  "adam_step: parameter %d: conv row of %d floats too large for LDS (16384)", i, d.C * d.R * d.S);
+    if (!q.w_crsk) continue;
+    SQR_CHECK_ARG(d.K % 64 == 0 && d.C % 64 == 0, "adam_step: parameter %d: dgrad packing needs K, C multiples of 64",
+                  i);
+    SQR_CHECK_ARG(++ncj <= MAXCJ, "adam_step: parameter %d: more than %d dgrad-packing convs in one call", i, MAXCJ);
+  }
+  return 0;
+}
+
 extern "C" int sqr_adam_step_amp(const sqr_adam_param* params, int nparams, double lr, double beta1,
                                  double beta2, double eps, double grad_scale, const float* loss_scale,
                                  const int* found_inf, void* stream) {
-  SQR_CHECK_ARG(params && nparams >= 0 && nparams <= 80, "adam_step: 0 <= nparams <= 80");
+  if (const int rc = check_adam_params(params, nparams)) return rc;
   hipStream_t st = as_stream(stream);
   size_t maxlds = 16;
   CJobs cj;
@@ -349,8 +377,6 @@ extern "C" int sqr_adam_step_amp(const sqr_adam_param* params, int nparams, doub
     int blocks = 0;
     for (int i = i0; i < nparams && i < i0 + MAXJ; ++i) {
       const sqr_adam_param& q = params[i];
-      SQR_CHECK_ARG(q.p && q.g && q.exp_avg && q.exp_avg_sq && q.step && q.n > 0 && q.n < (1ll << 31),
-                    "adam_step: parameter %d: null pointer or bad size", i);
       Job& jb = J.j[J.njobs];
       jb.p = q.p;
       jb.g = q.g;
@@ -369,9 +395,6 @@ extern "C" int sqr_adam_step_amp(const sqr_adam_param* params, int nparams, doub
       int nb;
       if (q.w_krsc) {
         const sqr_conv_desc& d = q.desc;
-        SQR_CHECK_ARG((d.dtype == SQR_DTYPE_BF16 || d.dtype == SQR_DTYPE_F16) &&
-                          (long long)d.K * d.C * d.R * d.S == q.n && d.stride <= 2,
-                      "adam_step: parameter %d: packing needs a bf16 / fp16 descriptor matching the weight", i);
         jb.K = d.K;
         jb.C = d.C;
         jb.RS = d.R * d.S;
@@ -381,12 +404,9 @@ extern "C" int sqr_adam_step_amp(const sqr_adam_param* params, int nparams, doub
           while (kp < d.R * d.S * d.C) kp *= 2;
         }
         jb.Kp = kp;
-        SQR_CHECK_ARG((size_t)jb.C * jb.RS * 4 <= 64 * 1024, "adam_step: conv row too large for LDS");
         maxlds = maxlds > (size_t)jb.C * jb.RS * 4 ? maxlds : (size_t)jb.C * jb.RS * 4;
         nb = d.K;
         if (q.w_crsk) {
-          SQR_CHECK_ARG(d.K % 64 == 0 && d.C % 64 == 0 && cj.njobs < 24,
-                        "adam_step: parameter %d: dgrad packing needs K, C multiples of 64", i);
           CJob& c = cj.j[cj.njobs];
           c.krsc = (const uint16_t*)q.w_krsc;
           c.crsk = (uint16_t*)q.w_crsk;

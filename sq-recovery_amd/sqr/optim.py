@@ -19,6 +19,12 @@ from ._lib import SqrAdamParam, check, lib, ptr, stream_ptr
 from .conv import DT_BF16, DT_F16, Conv2d, _desc, mark_packed, packed_buffers
 
 
+# limits of one sqr_adam_step call (sqr_optim.hip: MAXP, MAXCJ, and a conv row held in 64 KiB of LDS)
+MAX_PARAMS = 80
+MAX_DGRAD_PACKS = 24
+MAX_PACK_ROW = 16384
+
+
 class Adam(torch.optim.Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
         for k in ("fused", "foreach", "capturable"):
@@ -58,6 +64,41 @@ class Adam(torch.optim.Adam):
             st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return st
 
+    def _pack_request(self, p):
+        """(module, dtype, descriptor, krsc, crsk) when the step is to write this conv weight's packed
+        copies itself, else None: the weight is then repacked by sqr.conv.pack_all / the next forward
+        (its version counter moves with every step).  The kernels pack C < 8 (im2col rows) or K, C
+        multiples of 64, and rows (C R S floats) that fit the 64 KiB of LDS one workgroup may use."""
+        conv = self._convs.get(id(p))
+        if conv is None or conv[0].weight is not p:
+            return None
+        m, dt = conv
+        K, C, R, S = p.shape
+        d = _desc(1, C, R, R, K, R, S, m.stride[0], m.padding[0], dt)
+        if d.dtype not in (DT_BF16, DT_F16) or not (C < 8 or (K % 64 == 0 and C % 64 == 0)):
+            return None
+        if C * R * S > MAX_PACK_ROW or m.stride[0] > 2:
+            return None
+        krsc, crsk = packed_buffers(m, dt)
+        return m, dt, d, krsc, crsk
+
+    def _chunks(self, ps):
+        """Split a group's parameters into sqr_adam_step calls: at most MAX_PARAMS parameters and at
+        most MAX_DGRAD_PACKS convs whose backward-data layout the call writes.  -> lists of
+        (parameter, pack request or None)."""
+        out, cur, ncrsk = [], [], 0
+        for p in ps:
+            req = self._pack_request(p)
+            dgrad = req is not None and req[4] is not None
+            if len(cur) == MAX_PARAMS or (dgrad and ncrsk == MAX_DGRAD_PACKS):
+                out.append(cur)
+                cur, ncrsk = [], 0
+            cur.append((p, req))
+            ncrsk += dgrad
+        if cur:
+            out.append(cur)
+        return out
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -85,11 +126,11 @@ class Adam(torch.optim.Adam):
         for group, ps in groups:
             b1, b2 = group["betas"]
             lr = float(group["lr"])
-            for i0 in range(0, len(ps), 80):
-                chunk = ps[i0:i0 + 80]
+            for reqs in self._chunks(ps):
+                chunk = [p for p, _ in reqs]
                 arr = (SqrAdamParam * len(chunk))()
                 packed = []
-                for j, p in enumerate(chunk):
+                for j, (p, req) in enumerate(reqs):
                     st = self._state(p)
                     if st["step"].device != p.device or st["step"].dtype != torch.float32:
                         st["step"] = st["step"].to(device=p.device, dtype=torch.float32)
@@ -97,16 +138,11 @@ class Adam(torch.optim.Adam):
                     a.p, a.g = p.data_ptr(), p.grad.data_ptr()
                     a.exp_avg, a.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
                     a.step, a.n = st["step"].data_ptr(), p.numel()
-                    conv = self._convs.get(id(p))
-                    if conv is not None and conv[0].weight is p:
-                        m, dt = conv
-                        krsc, crsk = packed_buffers(m, dt)
-                        K, C, R, S = p.shape
-                        a.desc = _desc(1, C, R, R, K, R, S, m.stride[0], m.padding[0], dt)
-                        if a.desc.dtype in (DT_BF16, DT_F16) and (C < 8 or (K % 64 == 0 and C % 64 == 0)):
-                            a.w_krsc = krsc.data_ptr()
-                            a.w_crsk = crsk.data_ptr() if crsk is not None else None
-                            packed.append((m, dt))
+                    if req is not None:
+                        m, dt, a.desc, krsc, crsk = req
+                        a.w_krsc = krsc.data_ptr()
+                        a.w_crsk = crsk.data_ptr() if crsk is not None else None
+                        packed.append((m, dt))
                 if self.sqr_amp is not None:
                     scale, found_inf = self.sqr_amp
                     check(L.sqr_adam_step_amp(arr, len(chunk), lr, float(b1), float(b2), float(group["eps"]),

@@ -45,6 +45,7 @@ def test_grad_scaler_matches_torch():
     for p, q in zip(params, ref):
         assert float(opt.state[p]["step"]) == float(ropt.state[q]["step"]) == 8.0  # two skipped steps
         assert _rel(opt.state[p]["exp_avg_sq"], ropt.state[q]["exp_avg_sq"]) <= 1e-6
+        assert _rel(opt.state[p]["exp_avg"], ropt.state[q]["exp_avg"]) <= 1e-6
     assert sc.state_dict()["_growth_tracker"] == rsc.state_dict()["_growth_tracker"]
 
 

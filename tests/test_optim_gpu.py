@@ -39,6 +39,7 @@ def test_adam_matches_torch_and_packs():
     for k, st in sd["state"].items():
         assert set(st) == set(rsd["state"][k]) and float(st["step"]) == 3.0
         assert _rel(st["exp_avg_sq"], rsd["state"][k]["exp_avg_sq"]) <= 1e-6
+        assert _rel(st["exp_avg"], rsd["state"][k]["exp_avg"]) <= 1e-6
     # packed bf16 copies written by the step == a fresh pack of the updated weight
     for m in net.modules():
         if isinstance(m, sc.Conv2d):
