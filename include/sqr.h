@@ -17,6 +17,8 @@
  *                              + its autograd backward (analytic here)
  *   sqr_implicit_render        torch/classes.py:232-282  ImplicitLoss.depth_projection (forward only)
  *   sqr_explicit_loss_fwd_bwd  torch/classes.py:109-201  ExplicitLoss (occupancy :138-189, __call__ :191-201)
+ *   sqr_least_squares_fwd_bwd  torch/classes.py:297-371  LeastSquares (energy_function :318-356, __call__
+ *                              :358-371) + its autograd backward (analytic here)
  *   sqr_iou_counts             torch/classes.py:374-447  IoUAccuracy (ins_outs :394-426, __call__ :428-447)
  *   sqr_conv2d_fwd / _bwd_data / _bwd_weight
  *                              torch.nn.Conv2d as used by torchvision resnet18 inside ResNetSQ
@@ -115,6 +117,25 @@ int sqr_explicit_loss_fwd_bwd(const float* p_true, const float* p_pred, int B, i
 int sqr_explicit_loss_fwd_bwd_mean(const float* p_true, const float* p_pred, int B, int R, int need_grad,
                                    double* loss_per_sample, double* loss_mean, float* grad_pred, void* workspace,
                                    size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_least_squares_fwd_bwd for B samples at render size R. */
+size_t sqr_least_squares_workspace_bytes(int B, int R);
+
+/* LeastSquares(R)(target, params) and d loss / d params (Solina-Bajcsy energy, classes.py:297-371).
+ *   params  [B,12] f32, target [B,H,W] f32 : as sqr_implicit_loss_fwd_bwd
+ *   the point of resized pixel (r, c) is (c / R, 1 - r / R, z), z = its nearest-resampled value; it
+ *   counts iff z > 0 (a NaN pixel does not)
+ *   loss_per_sample [B] f64 : E_b = a0 a1 a2 * sum_points (F - 1)^2, F the inside-outside value of the
+ *                             clamped SQ; 0 for an image without points.  The reference loss is their mean
+ *   grad_params [B,12] f32 : d(mean_b E_b)/d params   (written only when need_grad != 0)
+ * Every sum is float64 in a fixed order (bitwise reproducible).  1 <= R <= 1024; H,W >= 1. */
+int sqr_least_squares_fwd_bwd(const float* params, const float* target, int B, int H, int W, int R,
+                              int need_grad, double* loss_per_sample, float* grad_params, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* ... with the batch mean (as sqr_implicit_loss_fwd_bwd_mean) */
+int sqr_least_squares_fwd_bwd_mean(const float* params, const float* target, int B, int H, int W, int R,
+                                   int need_grad, double* loss_per_sample, double* loss_mean, float* grad_params,
+                                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* IoUAccuracy(R): per-sample voxel counts [B,2] int64 = (|in_true & in_pred|, |in_true | in_pred|),
  * computed in float64 like the reference. */

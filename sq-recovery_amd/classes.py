@@ -5,14 +5,15 @@ metric math runs as fused HIP kernels on MI355X (libsqr, include/sqr.h):
 
   ImplicitLoss  classes.py:203-295 -> sqr_implicit_loss_fwd_bwd (render + MAE + analytic grad)
   ExplicitLoss  classes.py:109-201 -> sqr_explicit_loss_fwd_bwd
+  LeastSquares  classes.py:297-371 -> sqr_least_squares_fwd_bwd (point-set energy + analytic grad)
   IoUAccuracy   classes.py:374-447 -> sqr_iou_counts (float64, exact voxel counts)
   H5Dataset     classes.py:22-93   (data boundary, not accelerated; h5py imported lazily)
-  QuaternionLoss, LeastSquares     (not on the hot path; plain torch)
+  QuaternionLoss                   (not on the hot path; plain torch)
 
 CUDA tensors run on the kernels only (a missing libsqr raises; nothing falls back).  CPU tensors —
 the reference's CPU configuration (BASELINE config 1) — run the float64 host implementation in
-sqr/cpu.py (batched restatement of the same math, pinned to the reference's fixtures); mixing
-devices raises.
+sqr/cpu.py (batched restatement of the same math, pinned to the reference's fixtures; LeastSquares:
+the reference's own per-image torch code, in pred's dtype); mixing devices raises.
 """
 import glob
 import os
@@ -271,7 +272,11 @@ class IoUAccuracy:
 
 class LeastSquares:
     """classes.py:297-371 — Solina-Bajcsy energy between the depth-image point set and the
-    predicted SQ.  Not on the hot path (ragged per-image point sets); plain torch."""
+    predicted SQ: mean_b a0 a1 a2 sum_points (F - 1)^2, the points being the pixels > 0 of the
+    nearest-resized image.  Needs no label.  CUDA tensors run the HIP kernel (one thread per resized
+    pixel instead of ragged point sets: no host wait, capturable in a HIP graph); CPU tensors run the
+    reference's per-image torch code below.  Returns a 0-d tensor of pred's dtype, like the reference
+    (which computes in it; the kernel's float64 mean is rounded once)."""
 
     def __init__(self, render_size, device, reduce=True):
         self.render_size = render_size
@@ -296,7 +301,8 @@ class LeastSquares:
             out.append(((torch.sqrt(a[0] * a[1] * a[2]) * (f - 1)) ** 2).sum())
         return torch.stack(out)
 
-    def __call__(self, true, pred):
+    def batch_points(self, true):
+        """classes.py:358-369: per image the [3,N_i] points (c / R, 1 - r / R, z) of its resized pixels > 0."""
         R = self.render_size
         tr = F.interpolate(true, size=(R, R), mode="nearest")
         pts = []
@@ -304,4 +310,9 @@ class LeastSquares:
             rows, cols = torch.where(tr[i][0] > 0)
             z = tr[i][0][rows, cols]
             pts.append(torch.stack([cols.float() / R, 1 - rows.float() / R, z]))
-        return self.energy_function(pts, pred).mean()
+        return pts
+
+    def __call__(self, true, pred):
+        if not _on_cpu(true, pred):
+            return _L.least_squares(true, pred, self.render_size).to(pred.dtype)
+        return self.energy_function(self.batch_points(true), pred).mean()

@@ -1,5 +1,6 @@
 // Fused superquadric losses for gfx950: ImplicitLoss (render + MAE + analytic gradient),
-// ExplicitLoss (occupancy MSE + gradient) and IoUAccuracy counts.
+// ExplicitLoss (occupancy MSE + gradient), LeastSquares (point-set energy + gradient) and IoUAccuracy
+// counts.
 //
 // Reference algorithm (timoblak/sq-recovery, torch/):
 //   grid               classes.py:217-222 (linspace, exact 0 -> 1e-4), :121-126 (arange, R+1 points)
@@ -9,6 +10,7 @@
 //                      A=A1^(1/e2), B=B1^(1/e2), C=C1^(1/e1), E=(A+B)^(e2/e1), G=(E+C)^e1
 //   occupancy          classes.py:274 sigmoid(s (1-G)); ray model :277-279
 //   loss               classes.py:284-295 (nearest resize, mean |true - D|, mean over batch)
+//   least squares      classes.py:318-371 (points of the resized pixels > 0, a0 a1 a2 sum (F - 1)^2)
 //
 // MI355X design.  The grid is generated from the voxel index (no HBM reads), so the kernel is
 // bound by VALU transcendentals, not HBM: per voxel ~11 v_exp/v_log for the forward chain and ~7
@@ -193,9 +195,9 @@ struct Moments {
 //   m[3], m[4]  dL/de1, dL/de2 partials
 //   m[5..7]  sum gu_i              (sum dL/dv_i = m / a_i)
 //   m[8+3i+j] sum gu_i * g_j       (dL/dRc_ij = m/a_i - sum(dL/dv_i) t_j)
-__device__ __forceinline__ void vox_bwd(const SQ& s, const Vox& f, float occ, float omo, float gocc,
-                                        float sharp, float gx, float gy, float gz, Moments& M) {
-  const float hG = gocc * (-sharp) * occ * omo * f.G;  // dL/dln G
+// (vox_bwd_lnG: from hG = dL/dln G on; vox_bwd: from dL/docc)
+__device__ __forceinline__ void vox_bwd_lnG(const SQ& s, const Vox& f, float hG, float gx, float gy, float gz,
+                                            Moments& M) {
   const float g_lnF = hG * s.e1;
   const float g_lnE = g_lnF * f.rE;
   const float g_lnC = g_lnF * f.rC;
@@ -226,6 +228,10 @@ __device__ __forceinline__ void vox_bwd(const SQ& s, const Vox& f, float occ, fl
   M.m[14] = fmaf(gu2, gx, M.m[14]);
   M.m[15] = fmaf(gu2, gy, M.m[15]);
   M.m[16] = fmaf(gu2, gz, M.m[16]);
+}
+__device__ __forceinline__ void vox_bwd(const SQ& s, const Vox& f, float occ, float omo, float gocc,
+                                        float sharp, float gx, float gy, float gz, Moments& M) {
+  vox_bwd_lnG(s, f, gocc * (-sharp) * occ * omo * f.G, gx, gy, gz, M);  // dL/dln G
 }
 
 // block-wide sum of kNAcc floats -> out (thread 0..kNAcc-1 write)
@@ -592,6 +598,109 @@ __global__ void __launch_bounds__(NT) explicit_loss_kernel(const float* __restri
   block_reduce_store<NT>(vals, red, partials + ((size_t)b * gridDim.x + blockIdx.x) * kNAcc);
 }
 
+// -------------------------------------------------------------------------- LeastSquares
+// Solina-Bajcsy energy of the depth image's points against the SQ (classes.py:297-371):
+// E_b = a0 a1 a2 sum_points (F - 1)^2 over the nearest-resized pixels with z > 0, the point of pixel
+// (r, c) being (c / R, 1 - r / R, z).  The reference gathers the points per image (torch.where: ragged,
+// one host wait per image); here every resized pixel is a thread and a pixel that is not > 0 (NaN
+// included) adds exact zeros, which is the same sum.  Per point the chain is vox_fwd's and the Jacobian
+// vox_bwd_lnG's with dE/dln F = 2 (F - 1) F; the factor a0 a1 a2 and its own derivative E_b / a_i are
+// applied in the finalize, in float64.
+
+// 2^l - 1 without rounding 2^l first: points of a good fit lie on the surface, where F -> 1 and the
+// energy is all cancellation.  |x| < 1/4: the exponential series to x^9 (next term < 1e-11 x).
+__device__ __forceinline__ float exp2m1(float l) {
+  const float x = l * kLn2;
+  if (fabsf(x) >= 0.25f) return fexp2(l) - 1.f;
+  float p = 1.f / 362880.f;
+  p = fmaf(p, x, 1.f / 40320.f);
+  p = fmaf(p, x, 1.f / 5040.f);
+  p = fmaf(p, x, 1.f / 720.f);
+  p = fmaf(p, x, 1.f / 120.f);
+  p = fmaf(p, x, 1.f / 24.f);
+  p = fmaf(p, x, 1.f / 6.f);
+  p = fmaf(p, x, 0.5f);
+  return fmaf(p * x, x, x);
+}
+
+// grid: (blocks_per_sample, B); one thread per resized pixel.  partials: [B][nblk][kNAcc] float64 (a
+// thread's terms are fp32; every sum of them is float64 in a fixed order: lanes by DPP, waves in order)
+template <int NT>
+__global__ void __launch_bounds__(NT) least_squares_kernel(const float* __restrict__ params,
+                                                           const float* __restrict__ target, int H, int W,
+                                                           int R, double* __restrict__ partials) {
+  __shared__ double red[(NT / 64) * kNAcc];
+  const int b = blockIdx.y;
+  SQ s;
+  sq_load(params + 12 * b, s);
+  float vals[kNAcc];
+#pragma unroll
+  for (int i = 0; i < kNAcc; ++i) vals[i] = 0.f;
+  const int pix = blockIdx.x * NT + threadIdx.x;
+  if (pix < R * R) {
+    const int r = pix / R, c = pix - r * R;
+    // F.interpolate nearest (float scale, floor, clamp), as implicit_loss_kernel
+    const float sh = (float)H / (float)R, sw = (float)W / (float)R;
+    const int sr = min((int)floorf((float)r * sh), H - 1);
+    const int sc = min((int)floorf((float)c * sw), W - 1);
+    const float z = target[((size_t)b * H + sr) * W + sc];
+    if (z > 0.f) {  // classes.py:363 (false for NaN)
+      const float gx = (float)c / (float)R, gy = 1.f - (float)r / (float)R;  // classes.py:365-368, fp32
+      Vox f;
+      vox_fwd(s, gx - s.t[0], gy - s.t[1], z - s.t[2], f);
+      const float fm1 = exp2m1(s.e1 * f.lF);
+      vals[17] = fm1 * fm1;
+      Moments M;
+      M.zero();
+      vox_bwd_lnG(s, f, 2.f * fm1 * f.G, gx, gy, z, M);
+#pragma unroll
+      for (int i = 0; i < 17; ++i) vals[i] = M.m[i];
+    }
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < kNAcc; ++i) {
+    const double v = wave_sum_d((double)vals[i]);
+    if (lane == 0) red[wid * kNAcc + i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kNAcc) {
+    double acc = 0.0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) acc += red[w * kNAcc + threadIdx.x];
+    partials[((size_t)b * gridDim.x + blockIdx.x) * kNAcc + threadIdx.x] = acc;
+  }
+}
+
+// per sample: the blocks' partials in order, E_b = a0 a1 a2 * sum (F - 1)^2, and the gradient of the
+// batch mean: the moments scaled by a0 a1 a2 / B plus the direct term E_b / a_i (finalize_sample forms
+// dL/da_i = -acc[i] / a_i, so the term enters as acc[i] -= sum (F - 1)^2), through finalize_sample's
+// clamp masks and quaternion chain.  loss_mean as loss_finalize_kernel.
+__global__ void least_squares_finalize_kernel(const float* __restrict__ params, const double* __restrict__ partials,
+                                              int B, int nblk, int need_grad, double* __restrict__ loss_out,
+                                              float* __restrict__ grad_out, double* __restrict__ loss_mean) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  double loss = 0.0;
+  if (b < B) {
+    double acc[kNAcc];
+    for (int i = 0; i < kNAcc; ++i) acc[i] = 0.0;
+    for (int k = 0; k < nblk; ++k) {
+      const double* src = partials + ((size_t)b * nblk + k) * kNAcc;
+      for (int i = 0; i < kNAcc; ++i) acc[i] += src[i];
+    }
+    const float* p = params + 12 * b;
+    const double vol = (double)clampf(p[0], 0.05f, 1.f) * (double)clampf(p[1], 0.05f, 1.f) *
+                       (double)clampf(p[2], 0.05f, 1.f);
+    loss = vol * acc[17];
+    loss_out[b] = loss;
+    if (need_grad) {
+      for (int i = 0; i < 3; ++i) acc[i] -= acc[17];
+      finalize_sample(p, acc, vol / (double)B, grad_out + 12 * b);
+    }
+  }
+  if (loss_mean && gridDim.x == 1) block_mean(loss, B, loss_mean);
+}
+
 // -------------------------------------------------------------------------- IoUAccuracy (f64)
 struct SQd {
   double a[3], e1, e2, ie1, ie2, r21, tr[3], M[9];
@@ -806,6 +915,53 @@ extern "C" int sqr_explicit_loss_fwd_bwd(const float* p_true, const float* p_pre
                                          void* workspace, size_t workspace_bytes, void* stream) {
   return sqr_explicit_loss_fwd_bwd_mean(p_true, p_pred, B, R, need_grad, loss_per_sample, nullptr, grad_pred,
                                         workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t sqr_least_squares_workspace_bytes(int B, int R) {
+  if (B <= 0 || R <= 0) return 0;
+  const size_t nblk = ((size_t)R * R + 255) / 256;
+  return (size_t)B * nblk * kNAcc * sizeof(double);
+}
+
+extern "C" int sqr_least_squares_fwd_bwd_mean(const float* params, const float* target, int B, int H, int W,
+                                              int R, int need_grad, double* loss_per_sample, double* loss_mean,
+                                              float* grad_params, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  SQR_CHECK_ARG(B >= 1 && B <= 65535, "least_squares: B=%d out of range [1,65535]", B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "least_squares: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "least_squares: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(params && target && loss_per_sample && workspace, "least_squares: null pointer");
+  SQR_CHECK_ARG(!need_grad || grad_params, "least_squares: null grad_params");
+  const size_t need = sqr_least_squares_workspace_bytes(B, R);
+  if (workspace_bytes < need) {
+    set_error("least_squares: workspace %zu < %zu bytes", workspace_bytes, need);
+    return SQR_E_WORKSPACE;
+  }
+  hipStream_t st = as_stream(stream);
+  const int nblk = (R * R + 255) / 256;
+  double* partials = (double*)workspace;
+  // (the gradient moments are computed whether or not they are wanted, as for the other two losses:
+  // the loss value must not depend on need_grad)
+  hipLaunchKernelGGL((least_squares_kernel<256>), dim3(nblk, B), dim3(256), 0, st, params, target, H, W, R,
+                     partials);
+  SQR_HIP_LAUNCH_CHECK("least_squares_kernel");
+  if (loss_mean && B <= 1024) {
+    hipLaunchKernelGGL(least_squares_finalize_kernel, dim3(1), dim3((B + 63) / 64 * 64), 0, st, params, partials, B,
+                       nblk, need_grad, loss_per_sample, grad_params, loss_mean);
+  } else {
+    hipLaunchKernelGGL(least_squares_finalize_kernel, dim3((B + 63) / 64), dim3(64), 0, st, params, partials, B,
+                       nblk, need_grad, loss_per_sample, grad_params, (double*)nullptr);
+    if (loss_mean) hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(1024), 0, st, loss_per_sample, B, loss_mean);
+  }
+  SQR_HIP_LAUNCH_CHECK("least_squares_finalize_kernel");
+  return SQR_OK;
+}
+
+extern "C" int sqr_least_squares_fwd_bwd(const float* params, const float* target, int B, int H, int W, int R,
+                                         int need_grad, double* loss_per_sample, float* grad_params,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return sqr_least_squares_fwd_bwd_mean(params, target, B, H, W, R, need_grad, loss_per_sample, nullptr,
+                                        grad_params, workspace, workspace_bytes, stream);
 }
 
 template <typename P>

@@ -3,7 +3,7 @@
 The kernels compute the loss AND its parameter gradient in one pass (the gradient is
 d(batch-mean loss)/d params); the batch mean itself comes out of the same finalize launch, and
 backward() only scales the gradient by the upstream gradient (one sqr_loss_grad_scale launch).
-Reference: torch/classes.py:109-295 (timoblak/sq-recovery).
+Reference: torch/classes.py:109-371 (timoblak/sq-recovery).
 """
 import torch
 
@@ -27,26 +27,31 @@ def _scale_grad(grad, gout, dtype):
     return out if dtype == torch.float32 else out.to(dtype)
 
 
+def _image_target(target, params):
+    """The [B,H,W] view of a [B,1,H,W] / [B,H,W] image target of [B,12] params, and B, H, W."""
+    B = params.shape[0]
+    if params.dim() != 2 or params.shape[1] != 12:
+        raise ValueError("params must be [B,12], got %s" % (tuple(params.shape),))
+    if target.dim() == 4:
+        if target.shape[1] != 1:
+            raise ValueError("target must be [B,1,H,W], got %s" % (tuple(target.shape),))
+        tgt = target[:, 0]
+    elif target.dim() == 3:
+        tgt = target
+    else:
+        raise ValueError("target must be [B,1,H,W], got %s" % (tuple(target.shape),))
+    if tgt.shape[0] != B:
+        raise ValueError("batch mismatch: target %d vs params %d" % (tgt.shape[0], B))
+    return tgt, B, int(tgt.shape[1]), int(tgt.shape[2])
+
+
 class ImplicitLossFn(torch.autograd.Function):
     """loss = mean_b mean_rc |nearest(target)_b - render(params_b)|  (float64 scalar)."""
 
     @staticmethod
     def forward(ctx, target, params, R, tau, sharpness):
         _require_cuda(target, params)
-        B = params.shape[0]
-        if params.dim() != 2 or params.shape[1] != 12:
-            raise ValueError("params must be [B,12], got %s" % (tuple(params.shape),))
-        if target.dim() == 4:
-            if target.shape[1] != 1:
-                raise ValueError("target must be [B,1,H,W], got %s" % (tuple(target.shape),))
-            tgt = target[:, 0]
-        elif target.dim() == 3:
-            tgt = target
-        else:
-            raise ValueError("target must be [B,1,H,W], got %s" % (tuple(target.shape),))
-        if tgt.shape[0] != B:
-            raise ValueError("batch mismatch: target %d vs params %d" % (tgt.shape[0], B))
-        H, W = int(tgt.shape[1]), int(tgt.shape[2])
+        tgt, B, H, W = _image_target(target, params)
         p = params.detach().to(torch.float32).contiguous()
         t = tgt.detach().to(torch.float32).contiguous()
         need_grad = bool(ctx.needs_input_grad[1])
@@ -106,12 +111,55 @@ class ExplicitLossFn(torch.autograd.Function):
         return None, _scale_grad(grad, gout, ctx.params_dtype), None
 
 
+class LeastSquaresFn(torch.autograd.Function):
+    """E_b = a0 a1 a2 sum_points (F_b(point) - 1)^2 over the pixels > 0 of the nearest-resized target
+    (classes.py:297-371); returns mean_b E_b (float64 scalar) or, per_sample, the [B] energies."""
+
+    @staticmethod
+    def forward(ctx, target, params, R, per_sample):
+        _require_cuda(target, params)
+        tgt, B, H, W = _image_target(target, params)
+        p = params.detach().to(torch.float32).contiguous()
+        t = tgt.detach().to(torch.float32).contiguous()
+        need_grad = bool(ctx.needs_input_grad[1])
+        loss_ps = torch.empty(B, dtype=torch.float64, device=p.device)
+        loss = torch.empty((), dtype=torch.float64, device=p.device)  # the batch mean
+        grad = torch.empty(B, 12, dtype=torch.float32, device=p.device) if need_grad else None
+        L = lib()
+        wsb = L.sqr_least_squares_workspace_bytes(B, R)
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+        check(L.sqr_least_squares_fwd_bwd_mean(ptr(p), ptr(t), B, H, W, int(R), int(need_grad), ptr(loss_ps),
+                                               ptr(loss), ptr(grad), ptr(ws), wsb, stream_ptr(p.device)),
+              "sqr_least_squares_fwd_bwd_mean")
+        ctx.save_for_backward(grad)
+        ctx.params_dtype = params.dtype
+        ctx.is_per_sample = per_sample
+        return loss_ps if per_sample else loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        (grad,) = ctx.saved_tensors
+        if grad is None:
+            return None, None, None, None
+        if ctx.is_per_sample:
+            # the stored rows are d(mean_b E_b)/d params_b = (1/B) dE_b/d params_b
+            scale = (gout.to(torch.float32) * float(grad.shape[0])).unsqueeze(1)
+            return None, (grad * scale).to(ctx.params_dtype), None, None
+        return None, _scale_grad(grad, gout, ctx.params_dtype), None, None
+
+
 def implicit_loss(target, params, R, tau=1.0, sharpness=100.0):
     return ImplicitLossFn.apply(target, params, int(R), float(tau), float(sharpness))
 
 
 def explicit_loss(p_true, p_pred, R):
     return ExplicitLossFn.apply(p_true, p_pred, int(R))
+
+
+def least_squares(target, params, R, per_sample=False):
+    """LeastSquares(R)(target, params) as a float64 scalar; per_sample=True: the [B] energies E_b (both
+    differentiable w.r.t. params; no host synchronisation, so the call can be captured in a HIP graph)."""
+    return LeastSquaresFn.apply(target, params, int(R), bool(per_sample))
 
 
 def implicit_render(params, R, tau=1.0, sharpness=100.0):

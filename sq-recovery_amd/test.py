@@ -5,6 +5,10 @@ depth image with a trained ResNetSQ checkpoint (helpers.load_model format) on MI
 
 Prints size a and position t in pixel units (x255) like the reference (test.py:40-44).  The
 image window of the reference (cv2.imshow) is shown only with --show and OpenCV installed.
+
+--refine N polishes the prediction with N Adam steps (--refine-lr) down the LeastSquares energy of the
+image's own points (sqr.fit.refine, on the GPU) and prints the energy before and after and the refined
+parameters in the same format.  The energy goes down; the IoU against a label need not go up.
 """
 import argparse
 import os
@@ -33,6 +37,9 @@ def main(argv=None):
     ap.add_argument("--model", default="trained_models/model_explicit.pt")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--show", action="store_true")
+    ap.add_argument("--refine", type=int, default=0, metavar="N",
+                    help="refine the prediction with N Adam steps on the LeastSquares energy (CUDA)")
+    ap.add_argument("--refine-lr", type=float, default=2e-3)
     args = ap.parse_args(argv)
 
     net = ResNetSQ(outputs=4, pretrained=False).to(args.device)
@@ -48,6 +55,18 @@ def main(argv=None):
     print("Shape e:", e)
     print("Position t:", t * 255)
     print("Rotation q:", q)
+    if args.refine:
+        from sqr.fit import refine
+        x = torch.from_numpy(img.astype(np.float32)[None, None] / 255).to(args.device)
+        pred = torch.from_numpy(np.concatenate([a, e, t, q], 1)).to(args.device)
+        pred, before, after = refine(x, pred, steps=args.refine, lr=args.refine_lr)
+        a, e, t, q = (o.cpu().numpy() for o in torch.split(pred, (3, 2, 3, 4), dim=1))
+        print("Refined parameters (%d steps, LeastSquares energy %.6g -> %.6g): "
+              % (args.refine, before.item(), after.item()))
+        print("Size a:", a * 255)
+        print("Shape e:", e)
+        print("Position t:", t * 255)
+        print("Rotation q:", q)
     if args.show:
         import cv2
         cv2.imshow("image", img)

@@ -6,7 +6,8 @@ encoder.fc[0].weight.grad; per epoch a validation pass with the loss and IoUAccu
 ReduceLROnPlateau(patience 25) on the validation loss, checkpoint (helpers.save_model format)
 whenever the validation loss improves.  The loss is the reference's choice (train.py:62-64):
 --loss implicit (default: ImplicitLoss(R, tau 1.5, s 260)(images, pred)), explicit
-(ExplicitLoss(R)(labels, pred)) or combined (their sum, the visu.py pairing).
+(ExplicitLoss(R)(labels, pred)), combined (their sum, the visu.py pairing) or leastsquares
+(LeastSquares(R)(images, pred), classes.py:297-371: the label-free point-set energy).
 
 MI355X-specific:
   * on CUDA the convs / BatchNorm / losses run on the libsqr HIP kernels (nothing falls back);
@@ -39,7 +40,8 @@ import torch.utils.data as data
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from classes import ExplicitLoss, H5Dataset, ImplicitLoss, IoUAccuracy, SyntheticDataset  # noqa: E402
+from classes import (ExplicitLoss, H5Dataset, ImplicitLoss, IoUAccuracy, LeastSquares,  # noqa: E402
+                     SyntheticDataset)
 from helpers import load_model, parse_csv, save_compare_images, save_model  # noqa: E402
 from models import ResNetSQ  # noqa: E402
 from sqr import amp, dist  # noqa: E402
@@ -58,7 +60,8 @@ def parse_args(argv=None):
     ap.add_argument("--epochs", type=int, default=20000)
     ap.add_argument("--batch-size", type=int, default=32, help="per-GPU batch")
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--render-size", type=int, default=64, help="ImplicitLoss render size (train.py:64)")
+    ap.add_argument("--render-size", type=int, default=64,
+                    help="ImplicitLoss / LeastSquares render size (train.py:64)")
     ap.add_argument("--explicit-render-size", type=int, default=32, help="ExplicitLoss render size (train.py:62)")
     ap.add_argument("--log-interval", type=int, default=1)
     ap.add_argument("--running-mean", type=int, default=100)
@@ -66,7 +69,7 @@ def parse_args(argv=None):
     ap.add_argument("--continue-training", action="store_true")
     ap.add_argument("--bf16", action="store_true", help="bf16 autocast for the network")
     ap.add_argument("--fp16", action="store_true", help="fp16 autocast + dynamic loss scaling")
-    ap.add_argument("--loss", default="implicit", choices=("implicit", "explicit", "combined"),
+    ap.add_argument("--loss", default="implicit", choices=("implicit", "explicit", "combined", "leastsquares"),
                     help="training loss (reference train.py:62-64)")
     ap.add_argument("--device", default="auto", choices=("auto", "cuda", "cpu"))
     ap.add_argument("--compare-images", action="store_true",
@@ -135,12 +138,15 @@ def main(argv=None):
 
     implicit = ImplicitLoss(args.render_size, device, 1.5, 260)
     explicit = ExplicitLoss(args.explicit_render_size, device)
+    least_squares = LeastSquares(args.render_size, device)
 
     def loss_criterion(images, labels, pred):
         if args.loss == "implicit":
             return implicit(images, pred)
         if args.loss == "explicit":
             return explicit(labels, pred)
+        if args.loss == "leastsquares":
+            return least_squares(images, pred)
         return explicit(labels, pred) + implicit(images, pred)
 
     accuracy_estimator = IoUAccuracy(render_size=64, device=device, full=True)
