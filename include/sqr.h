@@ -19,6 +19,9 @@
  *   sqr_explicit_loss_fwd_bwd  torch/classes.py:109-201  ExplicitLoss (occupancy :138-189, __call__ :191-201)
  *   sqr_least_squares_fwd_bwd  torch/classes.py:297-371  LeastSquares (energy_function :318-356, __call__
  *                              :358-371) + its autograd backward (analytic here)
+ *   sqr_least_squares_normal_eq, sqr_lsq_lm_step, sqr_lsq_lm_refine
+ *                              no counterpart: Levenberg-Marquardt on the residuals behind LeastSquares'
+ *                              energy_function (classes.py:318-356), Solina & Bajcsy's own method
  *   sqr_iou_counts             torch/classes.py:374-447  IoUAccuracy (ins_outs :394-426, __call__ :428-447)
  *   sqr_conv2d_fwd / _bwd_data / _bwd_weight
  *                              torch.nn.Conv2d as used by torchvision resnet18 inside ResNetSQ
@@ -136,6 +139,54 @@ int sqr_least_squares_fwd_bwd(const float* params, const float* target, int B, i
 int sqr_least_squares_fwd_bwd_mean(const float* params, const float* target, int B, int H, int W, int R,
                                    int need_grad, double* loss_per_sample, double* loss_mean, float* grad_params,
                                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_least_squares_normal_eq for B samples at render size R. */
+size_t sqr_least_squares_normal_eq_workspace_bytes(int B, int R);
+
+/* Normal equations of the LeastSquares residuals r_k = sqrt(a0 a1 a2) (F(point_k) - 1), over the points
+ * of sqr_least_squares_fwd_bwd (same pixel rule, same resize arithmetic), for Levenberg-Marquardt:
+ *   energy [B] f64     : sum_k r_k^2 (the per-sample energy E_b)
+ *   Jtr    [B,12] f64  : sum_k J_k r_k (half the gradient of E_b)
+ *   JtJ    [B,12,12] f64 : sum_k J_k^T J_k, stored full, the lower triangle bitwise the upper one
+ * J_k = d r_k / d params_b (the 12 raw parameters), through the clamp masks (inclusive bounds) and the
+ * quaternion chain of the loss gradients; a parameter outside its range has a zero row and column in JtJ
+ * and a zero in Jtr.  A pixel that is not > 0 adds exact zeros; an image without points gives zeros.
+ * Every sum is float64 in a fixed order (bitwise reproducible), a sample's outputs do not depend on the
+ * rest of the batch.  1 <= R <= 1024; H,W >= 1. */
+int sqr_least_squares_normal_eq(const float* params, const float* target, int B, int H, int W, int R,
+                                double* JtJ, double* Jtr, double* energy, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* One Levenberg-Marquardt bookkeeping step per sample, float64 (one launch).
+ *   current state : params [B,12] f32, JtJ [B,12,12], Jtr [B,12], energy [B], lambda [B]   (in/out)
+ *   trial state   : params_trial [B,12] f32 (in when accept, out when solve), JtJ_trial, Jtr_trial,
+ *                   energy_trial (in)
+ *   accept != 0 : if energy_trial < energy (false for NaN) the trial becomes the current state,
+ *                 accepted[b] += 1 and lambda *= down; otherwise lambda *= up.  lambda stays in [1e-12, 1e12]
+ *   solve != 0  : delta [B,12] f64 solves (JtJ + lambda diag(JtJ)) delta = -Jtr on the free set
+ *                 {i : JtJ_ii > 0} (0 elsewhere), Jacobi-scaled, by Cholesky; a pivot that is not positive
+ *                 and finite (or a non-finite delta) gives delta = 0 and lambda *= up.  params_trial =
+ *                 project(params + delta): a, e, t clamped into [0.05,1], [0.1,1], [0,1], q divided by its
+ *                 norm (left alone if that is 0 or not finite), rounded to f32.
+ * up > 1, 0 < down < 1. */
+int sqr_lsq_lm_step(int B, int accept, int solve, double up, double down, float* params, double* JtJ, double* Jtr,
+                    double* energy, double* lambda, float* params_trial, const double* JtJ_trial,
+                    const double* Jtr_trial, const double* energy_trial, double* delta, int* accepted,
+                    void* stream);
+
+/* Workspace (bytes, device) needed by sqr_lsq_lm_refine for B samples at render size R. */
+size_t sqr_lsq_lm_refine_workspace_bytes(int B, int R);
+
+/* Levenberg-Marquardt refinement of B superquadrics on the LeastSquares residuals of their images:
+ * project the start, evaluate it, then `iters` rounds of sqr_lsq_lm_step + normal equations and a last
+ * accept, enqueued on `stream` as one linear chain (no host wait, no allocation: capturable).
+ *   params_out [B,12] f32, energy_before [B] f64 (at the projected start), energy_after [B] f64 (at
+ *   params_out, <= energy_before), accepted [B] i32 (accepted steps).
+ * Returns SQR_E_INVALID_ARG for B <= 0, R <= 0, iters < 0, lambda0 <= 0, up <= 1, down outside (0,1) or a
+ * short workspace; nothing is launched then. */
+int sqr_lsq_lm_refine(const float* params_in, const float* target, int B, int H, int W, int R, int iters,
+                      double lambda0, double up, double down, float* params_out, double* energy_before,
+                      double* energy_after, int* accepted, void* workspace, size_t workspace_bytes, void* stream);
 
 /* IoUAccuracy(R): per-sample voxel counts [B,2] int64 = (|in_true & in_pred|, |in_true | in_pred|),
  * computed in float64 like the reference. */

@@ -701,6 +701,272 @@ __global__ void least_squares_finalize_kernel(const float* __restrict__ params, 
   if (loss_mean && gridDim.x == 1) block_mean(loss, B, loss_mean);
 }
 
+// -------------------------------------------------------------------------- LeastSquares normal equations
+// Levenberg-Marquardt on the residuals r_k = sqrt(a0 a1 a2) (F(point_k) - 1) needs J^T J, J^T r and r^T r
+// per sample, J_k = d r_k / d raw params.  With v = a0 a1 a2, r_k = sqrt(v) f_k (f_k = F - 1) and
+// J_k = sqrt(v) j_k, j_k = dF/dparams + f_k / (2 a_i) on the three sizes, so all three products are v times
+// the Gram matrix of the rows [j_k | f_k]: each thread forms its pixel's row in fp32 (vox_fwd, vox_bwd_lnG at
+// dF/dln F = F, finalize_sample's chain applied per point), a wave lays its 64 rows out in LDS as a 64 x 16
+// tile [j (12) | f | 0 0 0] and takes tile^T tile with 16 v_mfma_f64_16x16x4_f64 (A and B are the same
+// register: lane l holds tile[4 s + (l >> 4)][l & 15] at step s; products of two floats are exact in
+// float64, every sum is float64 in the instruction's fixed order).  A pixel that is not > 0 is a zero row.
+// Waves are added in order per block, blocks in order per sample (lsq_normal_eq_finalize_kernel).
+constexpr int kNeqT = 16;            // tile width: 12 Jacobian columns, the residual, 3 zero columns
+constexpr int kNeqP = kNeqT * kNeqT;  // a block's partial: the whole 16 x 16 Gram matrix
+
+// (dx, dy, dz) = point - t.  The rotation's partial derivatives use d_j = g_j - t_j directly instead of
+// finalize_sample's (sum gu g_j) - (sum gu) t_j: per point there is nothing to cancel.
+__device__ __forceinline__ void lsq_point_row(const SQ& s, float dx, float dy, float dz, float* row) {
+  Vox f;
+  vox_fwd(s, dx, dy, dz, f);
+  const float fm1 = exp2m1(s.e1 * f.lF);
+  Moments M;
+  M.zero();
+  vox_bwd_lnG(s, f, f.G, dx, dy, dz, M);
+  float j[12];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) j[i] = (0.5f * fm1 - M.m[i]) * s.ia[i];
+  j[3] = M.m[3];
+  j[4] = M.m[4];
+  float sgv[3], gR[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    sgv[i] = M.m[5 + i] * s.ia[i];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gR[3 * i + k] = M.m[8 + 3 * i + k] * s.ia[i];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) j[5 + k] = -(s.M[k] * sgv[0] + s.M[3 + k] * sgv[1] + s.M[6 + k] * sgv[2]);
+  // vjp of mat_from_quaternion at conj(q) = (x,y,z,w), as finalize_sample
+  const float x = -s.q[0], y = -s.q[1], z = -s.q[2], w = s.q[3];
+  const float qx = 2 * y * (gR[1] + gR[3]) + 2 * z * (gR[2] + gR[6]) + 2 * w * (gR[7] - gR[5]) - 4 * x * (gR[4] + gR[8]);
+  const float qy = 2 * x * (gR[1] + gR[3]) + 2 * z * (gR[5] + gR[7]) + 2 * w * (gR[2] - gR[6]) - 4 * y * (gR[0] + gR[8]);
+  const float qz = 2 * x * (gR[2] + gR[6]) + 2 * y * (gR[5] + gR[7]) + 2 * w * (gR[3] - gR[1]) - 4 * z * (gR[0] + gR[4]);
+  const float qw = 2 * z * (gR[3] - gR[1]) + 2 * y * (gR[2] - gR[6]) + 2 * x * (gR[7] - gR[5]);
+  j[8] = -qx;
+  j[9] = -qy;
+  j[10] = -qz;
+  j[11] = qw;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) row[i] = s.mask[i] != 0.f ? j[i] : 0.f;  // clamped: an exactly zero column
+  row[12] = fm1;
+  row[13] = row[14] = row[15] = 0.f;
+}
+
+// grid: (blocks_per_sample, B); one thread per resized pixel.  partials: [B][nblk][16][16] float64
+template <int NT>
+__global__ void __launch_bounds__(NT) lsq_normal_eq_kernel(const float* __restrict__ params,
+                                                           const float* __restrict__ target, int H, int W, int R,
+                                                           double* __restrict__ partials) {
+  static_assert(NT == kNeqP, "one thread per entry of the block's Gram matrix");
+  typedef double d4 __attribute__((ext_vector_type(4)));
+  __shared__ float4 tile[NT / 64][64 * kNeqT / 4];
+  __shared__ double red[NT / 64][kNeqP];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  SQ s;
+  sq_load(params + 12 * b, s);
+  float row[kNeqT];
+#pragma unroll
+  for (int i = 0; i < kNeqT; ++i) row[i] = 0.f;
+  const int pix = blockIdx.x * NT + threadIdx.x;
+  if (pix < R * R) {
+    const int r = pix / R, c = pix - r * R;
+    // F.interpolate nearest (float scale, floor, clamp), as least_squares_kernel
+    const float sh = (float)H / (float)R, sw = (float)W / (float)R;
+    const int sr = min((int)floorf((float)r * sh), H - 1);
+    const int sc = min((int)floorf((float)c * sw), W - 1);
+    const float z = target[((size_t)b * H + sr) * W + sc];
+    if (z > 0.f) {  // classes.py:363 (false for NaN)
+      const float gx = (float)c / (float)R, gy = 1.f - (float)r / (float)R;
+      lsq_point_row(s, gx - s.t[0], gy - s.t[1], z - s.t[2], row);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < kNeqT / 4; ++i)
+    tile[wid][lane * (kNeqT / 4) + i] = make_float4(row[4 * i], row[4 * i + 1], row[4 * i + 2], row[4 * i + 3]);
+  __syncthreads();
+  const float* tw = reinterpret_cast<const float*>(tile[wid]);
+  d4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int st = 0; st < 16; ++st) {
+    const double v = (double)tw[(4 * st + (lane >> 4)) * kNeqT + (lane & 15)];
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v, v, acc, 0, 0, 0);
+  }
+  // f64 C/D layout: register i of lane l is row (l >> 4) + 4 i, column l & 15
+#pragma unroll
+  for (int i = 0; i < 4; ++i) red[wid][((lane >> 4) + 4 * i) * kNeqT + (lane & 15)] = acc[i];
+  __syncthreads();
+  double sum = 0.0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) sum += red[w][threadIdx.x];
+  partials[((size_t)b * gridDim.x + blockIdx.x) * kNeqP + threadIdx.x] = sum;
+}
+
+// grid: B blocks of 256 threads, thread (i, j) of a sample.  The blocks' partials in order, times a0 a1 a2;
+// entry (i, j) of JtJ is read at (min, max), so the lower triangle is the upper one bitwise.
+// e2 (nullable): a second copy of the energies.
+__global__ void __launch_bounds__(kNeqP) lsq_normal_eq_finalize_kernel(const float* __restrict__ params,
+                                                                       const double* __restrict__ partials, int nblk,
+                                                                       double* __restrict__ JtJ,
+                                                                       double* __restrict__ Jtr,
+                                                                       double* __restrict__ energy,
+                                                                       double* __restrict__ e2) {
+  const int b = blockIdx.x;
+  const int i = threadIdx.x / kNeqT, j = threadIdx.x % kNeqT;
+  if (i > 12 || j > 12) return;
+  const int src = min(i, j) * kNeqT + max(i, j);
+  double acc = 0.0;
+  for (int k = 0; k < nblk; ++k) acc += partials[((size_t)b * nblk + k) * kNeqP + src];
+  const float* p = params + 12 * b;
+  const double vol = (double)clampf(p[0], 0.05f, 1.f) * (double)clampf(p[1], 0.05f, 1.f) *
+                     (double)clampf(p[2], 0.05f, 1.f);
+  acc *= vol;
+  if (i < 12 && j < 12) JtJ[(size_t)b * 144 + i * 12 + j] = acc;
+  if (i == 12 && j < 12) Jtr[(size_t)b * 12 + j] = acc;
+  if (i == 12 && j == 12) {
+    energy[b] = acc;
+    if (e2) e2[b] = acc;
+  }
+}
+
+// -------------------------------------------------------------------------- Levenberg-Marquardt step
+// clamp a, e, t into their ranges and divide q by its norm (kept as it is when the norm is 0 or not finite)
+__device__ __forceinline__ void lm_project(const double* x, float* out) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    out[i] = clampf((float)x[i], 0.05f, 1.f);
+    out[5 + i] = clampf((float)x[5 + i], 0.f, 1.f);
+  }
+  out[3] = clampf((float)x[3], 0.1f, 1.f);
+  out[4] = clampf((float)x[4], 0.1f, 1.f);
+  const double n = sqrt(x[8] * x[8] + x[9] * x[9] + x[10] * x[10] + x[11] * x[11]);
+  const double inv = (n > 0.0 && isfinite(n)) ? 1.0 / n : 1.0;
+#pragma unroll
+  for (int i = 8; i < 12; ++i) out[i] = (float)(x[i] * inv);
+}
+
+__global__ void lm_init_kernel(const float* __restrict__ params_in, int B, double lambda0,
+                               float* __restrict__ params, double* __restrict__ lambda,
+                               int* __restrict__ accepted) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double x[12];
+  float o[12];
+  for (int i = 0; i < 12; ++i) x[i] = (double)params_in[12 * b + i];
+  lm_project(x, o);
+  for (int i = 0; i < 12; ++i) params[12 * b + i] = o[i];
+  lambda[b] = lambda0;
+  accepted[b] = 0;
+}
+
+constexpr double kLmLambdaMin = 1e-12, kLmLambdaMax = 1e12;
+__device__ __forceinline__ double lm_clamp_lambda(double l) { return fmin(fmax(l, kLmLambdaMin), kLmLambdaMax); }
+
+// one thread per sample, float64.  accept: the trial replaces the current state iff E_t < E (false for
+// NaN), lambda *= down, else lambda *= up.  solve: (H + lambda diag H) delta = -g on the free set
+// {i: H_ii > 0} as the Jacobi-scaled (S H S + lambda I) y = -S g, delta = S y, by Cholesky (an index off
+// the free set is an identity row with a zero right side: y_i = 0 exactly); a pivot that is not a positive
+// finite number, or a delta that is not finite, gives delta = 0 and lambda *= up.  The new trial
+// parameters are lm_project(p + delta).
+__global__ void __launch_bounds__(64) lm_step_kernel(int B, int accept, int solve, double up, double down,
+                                                     float* __restrict__ p, double* __restrict__ Hc,
+                                                     double* __restrict__ gc, double* __restrict__ Ec,
+                                                     double* __restrict__ lambda, float* __restrict__ p_t,
+                                                     const double* __restrict__ H_t, const double* __restrict__ g_t,
+                                                     const double* __restrict__ E_t, double* __restrict__ delta,
+                                                     int* __restrict__ accepted) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  p += 12 * (size_t)b;
+  p_t += 12 * (size_t)b;
+  Hc += 144 * (size_t)b;
+  gc += 12 * (size_t)b;
+  double lam = lambda[b];
+  if (accept) {
+    if (E_t[b] < Ec[b]) {
+      for (int i = 0; i < 144; ++i) Hc[i] = H_t[144 * (size_t)b + i];
+      for (int i = 0; i < 12; ++i) {
+        gc[i] = g_t[12 * (size_t)b + i];
+        p[i] = p_t[i];
+      }
+      Ec[b] = E_t[b];
+      accepted[b] += 1;
+      lam *= down;
+    } else {
+      lam *= up;
+    }
+    lam = lm_clamp_lambda(lam);
+  }
+  if (solve) {
+    // every loop unrolled and no early exit, so sc, L and y stay in registers (indexed at run time they
+    // live in scratch memory: 67 us per launch against 12 at B = 64); after a failed pivot the rest is
+    // computed on NaNs and thrown away
+    double sc[12], L[12][12], inv[12], y[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      const double d = Hc[13 * i];
+      sc[i] = d > 0.0 ? 1.0 / sqrt(d) : 0.0;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+#pragma unroll
+      for (int i = j; i < 12; ++i) {
+        double a;
+        if (sc[i] == 0.0 || sc[j] == 0.0)
+          a = i == j ? 1.0 : 0.0;
+        else
+          a = Hc[12 * j + i] * sc[i] * sc[j] + (i == j ? lam : 0.0);
+#pragma unroll
+        for (int k = 0; k < j; ++k) a -= L[i][k] * L[j][k];
+        if (i == j) {
+          ok = ok && a > 0.0 && isfinite(a);
+          L[j][j] = sqrt(a);
+          inv[j] = 1.0 / L[j][j];
+        } else {
+          L[i][j] = a * inv[j];
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {  // L z = -S g
+      double a = sc[i] == 0.0 ? 0.0 : -sc[i] * gc[i];
+#pragma unroll
+      for (int k = 0; k < i; ++k) a -= L[i][k] * y[k];
+      y[i] = a * inv[i];
+    }
+#pragma unroll
+    for (int i = 11; i >= 0; --i) {  // L^T y = z
+      double a = y[i];
+#pragma unroll
+      for (int k = i + 1; k < 12; ++k) a -= L[k][i] * y[k];
+      y[i] = a * inv[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      y[i] = sc[i] == 0.0 ? 0.0 : sc[i] * y[i];
+      ok = ok && isfinite(y[i]);
+    }
+    if (!ok) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) y[i] = 0.0;
+      lam = lm_clamp_lambda(lam * up);
+    }
+    double x[12];
+    float o[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      delta[12 * (size_t)b + i] = y[i];
+      x[i] = (double)p[i] + y[i];
+    }
+    lm_project(x, o);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) p_t[i] = o[i];
+  }
+  lambda[b] = lam;
+}
+
 // -------------------------------------------------------------------------- IoUAccuracy (f64)
 struct SQd {
   double a[3], e1, e2, ie1, ie2, r21, tr[3], M[9];
@@ -962,6 +1228,116 @@ extern "C" int sqr_least_squares_fwd_bwd(const float* params, const float* targe
                                          void* workspace, size_t workspace_bytes, void* stream) {
   return sqr_least_squares_fwd_bwd_mean(params, target, B, H, W, R, need_grad, loss_per_sample, nullptr,
                                         grad_params, workspace, workspace_bytes, stream);
+}
+
+static size_t normal_eq_blocks(int R) { return ((size_t)R * R + kNeqP - 1) / kNeqP; }
+
+extern "C" size_t sqr_least_squares_normal_eq_workspace_bytes(int B, int R) {
+  if (B <= 0 || R <= 0) return 0;
+  return (size_t)B * normal_eq_blocks(R) * kNeqP * sizeof(double);
+}
+
+// the two launches of the normal equations (arguments checked by the callers)
+static int launch_normal_eq(hipStream_t st, const float* params, const float* target, int B, int H, int W, int R,
+                            double* JtJ, double* Jtr, double* energy, double* energy_copy, double* partials) {
+  const int nblk = (int)normal_eq_blocks(R);
+  hipLaunchKernelGGL((lsq_normal_eq_kernel<kNeqP>), dim3(nblk, B), dim3(kNeqP), 0, st, params, target, H, W, R,
+                     partials);
+  SQR_HIP_LAUNCH_CHECK("lsq_normal_eq_kernel");
+  hipLaunchKernelGGL(lsq_normal_eq_finalize_kernel, dim3(B), dim3(kNeqP), 0, st, params, partials, nblk, JtJ, Jtr,
+                     energy, energy_copy);
+  SQR_HIP_LAUNCH_CHECK("lsq_normal_eq_finalize_kernel");
+  return SQR_OK;
+}
+
+extern "C" int sqr_least_squares_normal_eq(const float* params, const float* target, int B, int H, int W, int R,
+                                           double* JtJ, double* Jtr, double* energy, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(B >= 1 && B <= 65535, "least_squares_normal_eq: B=%d out of range [1,65535]", B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "least_squares_normal_eq: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "least_squares_normal_eq: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(params && target && JtJ && Jtr && energy && workspace, "least_squares_normal_eq: null pointer");
+  const size_t need = sqr_least_squares_normal_eq_workspace_bytes(B, R);
+  if (workspace_bytes < need) {
+    set_error("least_squares_normal_eq: workspace %zu < %zu bytes", workspace_bytes, need);
+    return SQR_E_WORKSPACE;
+  }
+  return launch_normal_eq(as_stream(stream), params, target, B, H, W, R, JtJ, Jtr, energy, nullptr,
+                          (double*)workspace);
+}
+
+extern "C" int sqr_lsq_lm_step(int B, int accept, int solve, double up, double down, float* params, double* JtJ,
+                               double* Jtr, double* energy, double* lambda, float* params_trial,
+                               const double* JtJ_trial, const double* Jtr_trial, const double* energy_trial,
+                               double* delta, int* accepted, void* stream) {
+  SQR_CHECK_ARG(B >= 1, "lsq_lm_step: B=%d must be >= 1", B);
+  SQR_CHECK_ARG(up > 1.0, "lsq_lm_step: up=%g must be > 1", up);
+  SQR_CHECK_ARG(down > 0.0 && down < 1.0, "lsq_lm_step: down=%g outside (0,1)", down);
+  SQR_CHECK_ARG(params && JtJ && Jtr && energy && lambda, "lsq_lm_step: null state pointer");
+  SQR_CHECK_ARG(!accept || (params_trial && JtJ_trial && Jtr_trial && energy_trial && accepted),
+                "lsq_lm_step: accept without a trial state");
+  SQR_CHECK_ARG(!solve || (params_trial && delta), "lsq_lm_step: solve without params_trial / delta");
+  hipLaunchKernelGGL(lm_step_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), B, accept, solve, up, down,
+                     params, JtJ, Jtr, energy, lambda, params_trial, JtJ_trial, Jtr_trial, energy_trial, delta,
+                     accepted);
+  SQR_HIP_LAUNCH_CHECK("lm_step_kernel");
+  return SQR_OK;
+}
+
+// float64 first, then the trial parameters: [JtJ 144][Jtr 12][lambda 1][JtJ_t 144][Jtr_t 12][E_t 1][delta 12]
+// per sample, the normal equations' partials, params_trial [B,12] f32
+constexpr size_t kLmDoubles = 144 + 12 + 1 + 144 + 12 + 1 + 12;
+
+extern "C" size_t sqr_lsq_lm_refine_workspace_bytes(int B, int R) {
+  if (B <= 0 || R <= 0) return 0;
+  return (size_t)B * kLmDoubles * sizeof(double) + sqr_least_squares_normal_eq_workspace_bytes(B, R) +
+         (size_t)B * 12 * sizeof(float);
+}
+
+extern "C" int sqr_lsq_lm_refine(const float* params_in, const float* target, int B, int H, int W, int R, int iters,
+                                 double lambda0, double up, double down, float* params_out, double* energy_before,
+                                 double* energy_after, int* accepted, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  SQR_CHECK_ARG(B >= 1 && B <= 65535, "lsq_lm_refine: B=%d out of range [1,65535]", B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "lsq_lm_refine: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "lsq_lm_refine: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(iters >= 0, "lsq_lm_refine: iters=%d must be >= 0", iters);
+  SQR_CHECK_ARG(lambda0 > 0.0, "lsq_lm_refine: lambda0=%g must be > 0", lambda0);
+  SQR_CHECK_ARG(up > 1.0, "lsq_lm_refine: up=%g must be > 1", up);
+  SQR_CHECK_ARG(down > 0.0 && down < 1.0, "lsq_lm_refine: down=%g outside (0,1)", down);
+  SQR_CHECK_ARG(params_in && target && params_out && energy_before && energy_after && accepted && workspace,
+                "lsq_lm_refine: null pointer");
+  const size_t need = sqr_lsq_lm_refine_workspace_bytes(B, R);
+  SQR_CHECK_ARG(workspace_bytes >= need, "lsq_lm_refine: workspace %zu < %zu bytes", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  const size_t nb = (size_t)B;
+  double* JtJ = (double*)workspace;
+  double* Jtr = JtJ + 144 * nb;
+  double* lambda = Jtr + 12 * nb;
+  double* JtJ_t = lambda + nb;
+  double* Jtr_t = JtJ_t + 144 * nb;
+  double* E_t = Jtr_t + 12 * nb;
+  double* delta = E_t + nb;
+  double* partials = delta + 12 * nb;
+  float* p_t = (float*)(partials + nb * normal_eq_blocks(R) * kNeqP);
+  hipLaunchKernelGGL(lm_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, params_in, B, lambda0, params_out, lambda,
+                     accepted);
+  SQR_HIP_LAUNCH_CHECK("lm_init_kernel");
+  int rc = launch_normal_eq(st, params_out, target, B, H, W, R, JtJ, Jtr, energy_after, energy_before, partials);
+  if (rc != SQR_OK) return rc;
+  for (int it = 0; it <= iters && iters > 0; ++it) {
+    // round it: accept the trial of the round before (none in round 0), solve for the next one and
+    // evaluate it; the last pass only accepts
+    const int accept = it > 0, solve = it < iters;
+    rc = sqr_lsq_lm_step(B, accept, solve, up, down, params_out, JtJ, Jtr, energy_after, lambda, p_t, JtJ_t, Jtr_t,
+                         E_t, delta, accepted, stream);
+    if (rc != SQR_OK) return rc;
+    if (solve) {
+      rc = launch_normal_eq(st, p_t, target, B, H, W, R, JtJ_t, Jtr_t, E_t, nullptr, partials);
+      if (rc != SQR_OK) return rc;
+    }
+  }
+  return SQR_OK;
 }
 
 template <typename P>

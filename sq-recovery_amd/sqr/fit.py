@@ -1,4 +1,5 @@
-"""Point-set refinement of predicted superquadrics: a few Adam steps down the LeastSquares energy.
+"""Point-set refinement of predicted superquadrics: descend the LeastSquares energy of the image's own
+points, with Adam (refine) or with Levenberg-Marquardt (refine_lm).
 
 The classical recovery (Solina & Bajcsy) fits a superquadric to the depth image's points by iterating
 on the energy a0 a1 a2 sum_points (F - 1)^2; the reference keeps that energy as its LeastSquares loss
@@ -6,21 +7,40 @@ on the energy a0 a1 a2 sum_points (F - 1)^2; the reference keeps that energy as 
 prediction: predict, then descend.  What this promises is a lower energy — a better fit of the
 visible points — not a higher IoU against a label: the depth image shows one side of the object.
 
-Everything runs on the device (sqr_least_squares_fwd_bwd per step plus a handful of elementwise
-launches on the [B,12] tensor); nothing is read back inside the loop.
+Everything runs on the device (Adam: sqr_least_squares_fwd_bwd per step plus a handful of elementwise
+launches on the [B,12] tensor; LM: sqr_lsq_lm_refine, one chain of normal-equations and step kernels);
+nothing is read back inside the loop.
 """
 import torch
 
-from .losses import least_squares
+from .losses import least_squares, lm_refine
 
 
-def refine(images, params, steps=200, lr=2e-3, render_size=32, betas=(0.9, 0.999), eps=1e-8):
+def refine_lm(images, params, iters=10, render_size=32, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
     """images [B,1,H,W] or [B,H,W], params [B,12] (CUDA) -> (refined [B,12] f32, energy_before [B] f64,
-    energy_after [B] f64).
+    energy_after [B] f64), with return_info also the accepted step counts [B] i32.
+
+    Levenberg-Marquardt, Solina & Bajcsy's method: damped Gauss-Newton on the residuals
+    sqrt(a0 a1 a2) (F(point) - 1), solving (J^T J + lambda diag(J^T J)) delta = -J^T r per sample.  A step
+    is kept only if it lowers the energy (lambda *= down), otherwise lambda *= up.  The start and every
+    trial are projected: a, e, t clamped into their ranges, q normalised, so the result is a unit
+    quaternion with in-range parameters, and energy_before is the energy at the projected start.  Every
+    sample is refined on its own; no host wait, so the call can be captured in a HIP graph."""
+    out, before, after, accepted = lm_refine(images, params, int(render_size), int(iters), lambda0, up, down)
+    return (out, before, after, accepted) if return_info else (out, before, after)
+
+
+def refine(images, params, steps=200, lr=2e-3, render_size=32, betas=(0.9, 0.999), eps=1e-8, method="adam"):
+    """images [B,1,H,W] or [B,H,W], params [B,12] (CUDA) -> (refined [B,12] f32, energy_before [B] f64,
+    energy_after [B] f64).  method "lm": refine_lm with `steps` iterations (lr, betas, eps unused).
 
     Adam (torch.optim.Adam's update, bias-corrected) on a detached copy of params.  The objective is
     the sum of the per-sample energies and Adam is elementwise, so every image is refined on its own:
     a sample's result does not depend on what else is in the batch."""
+    if method == "lm":
+        return refine_lm(images, params, iters=steps, render_size=render_size)
+    if method != "adam":
+        raise ValueError("refine: method must be 'adam' or 'lm', got %r" % (method,))
     R = int(render_size)
     p = params.detach().to(torch.float32).clone().requires_grad_(True)
     before = least_squares(images, p.detach(), R, per_sample=True)

@@ -162,6 +162,45 @@ def least_squares(target, params, R, per_sample=False):
     return LeastSquaresFn.apply(target, params, int(R), bool(per_sample))
 
 
+def least_squares_normal_eq(target, params, R):
+    """Normal equations of the LeastSquares residuals r_k = sqrt(a0 a1 a2) (F(point_k) - 1) per sample:
+    (H [B,12,12] = sum J_k^T J_k, g [B,12] = sum J_k r_k, E [B] = sum r_k^2), all float64, no autograd
+    (sqr_least_squares_normal_eq).  target [B,1,H,W] or [B,H,W], params [B,12], CUDA."""
+    _require_cuda(target, params)
+    tgt, B, H, W = _image_target(target, params)
+    p = params.detach().to(torch.float32).contiguous()
+    t = tgt.detach().to(torch.float32).contiguous()
+    JtJ = torch.empty(B, 12, 12, dtype=torch.float64, device=p.device)
+    Jtr = torch.empty(B, 12, dtype=torch.float64, device=p.device)
+    E = torch.empty(B, dtype=torch.float64, device=p.device)
+    L = lib()
+    wsb = L.sqr_least_squares_normal_eq_workspace_bytes(B, int(R))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+    check(L.sqr_least_squares_normal_eq(ptr(p), ptr(t), B, H, W, int(R), ptr(JtJ), ptr(Jtr), ptr(E), ptr(ws), wsb,
+                                        stream_ptr(p.device)), "sqr_least_squares_normal_eq")
+    return JtJ, Jtr, E
+
+
+def lm_refine(target, params, R, iters, lambda0, up, down):
+    """sqr_lsq_lm_refine -> (params [B,12] f32, energy_before [B] f64, energy_after [B] f64, accepted [B]
+    i32).  One chain of launches on the current stream; no host wait."""
+    _require_cuda(target, params)
+    tgt, B, H, W = _image_target(target, params)
+    p = params.detach().to(torch.float32).contiguous()
+    t = tgt.detach().to(torch.float32).contiguous()
+    out = torch.empty(B, 12, dtype=torch.float32, device=p.device)
+    before = torch.empty(B, dtype=torch.float64, device=p.device)
+    after = torch.empty(B, dtype=torch.float64, device=p.device)
+    accepted = torch.empty(B, dtype=torch.int32, device=p.device)
+    L = lib()
+    wsb = L.sqr_lsq_lm_refine_workspace_bytes(B, int(R))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+    check(L.sqr_lsq_lm_refine(ptr(p), ptr(t), B, H, W, int(R), int(iters), float(lambda0), float(up), float(down),
+                              ptr(out), ptr(before), ptr(after), ptr(accepted), ptr(ws), wsb, stream_ptr(p.device)),
+          "sqr_lsq_lm_refine")
+    return out, before, after, accepted
+
+
 def implicit_render(params, R, tau=1.0, sharpness=100.0):
     """depth_projection (classes.py:232-282) -> [B,R,R] float32 images (no autograd)."""
     _require_cuda(params)

@@ -9,6 +9,8 @@ image window of the reference (cv2.imshow) is shown only with --show and OpenCV 
 --refine N polishes the prediction with N Adam steps (--refine-lr) down the LeastSquares energy of the
 image's own points (sqr.fit.refine, on the GPU) and prints the energy before and after and the refined
 parameters in the same format.  The energy goes down; the IoU against a label need not go up.
+--refine-method lm runs N Levenberg-Marquardt iterations instead (sqr.fit.refine_lm): the energy is that
+of the projected prediction (a, e, t clamped, q normalised) and the result is a unit quaternion.
 """
 import argparse
 import os
@@ -40,6 +42,8 @@ def main(argv=None):
     ap.add_argument("--refine", type=int, default=0, metavar="N",
                     help="refine the prediction with N Adam steps on the LeastSquares energy (CUDA)")
     ap.add_argument("--refine-lr", type=float, default=2e-3)
+    ap.add_argument("--refine-method", choices=("adam", "lm"), default="adam",
+                    help="adam: N Adam steps; lm: N Levenberg-Marquardt iterations (sqr.fit.refine_lm)")
     args = ap.parse_args(argv)
 
     net = ResNetSQ(outputs=4, pretrained=False).to(args.device)
@@ -59,10 +63,14 @@ def main(argv=None):
         from sqr.fit import refine
         x = torch.from_numpy(img.astype(np.float32)[None, None] / 255).to(args.device)
         pred = torch.from_numpy(np.concatenate([a, e, t, q], 1)).to(args.device)
-        pred, before, after = refine(x, pred, steps=args.refine, lr=args.refine_lr)
+        pred, before, after = refine(x, pred, steps=args.refine, lr=args.refine_lr, method=args.refine_method)
         a, e, t, q = (o.cpu().numpy() for o in torch.split(pred, (3, 2, 3, 4), dim=1))
-        print("Refined parameters (%d steps, LeastSquares energy %.6g -> %.6g): "
-              % (args.refine, before.item(), after.item()))
+        if args.refine_method == "lm":
+            print("Refined parameters (%d Levenberg-Marquardt iterations, LeastSquares energy %.6g -> %.6g): "
+                  % (args.refine, before.item(), after.item()))
+        else:
+            print("Refined parameters (%d steps, LeastSquares energy %.6g -> %.6g): "
+                  % (args.refine, before.item(), after.item()))
         print("Size a:", a * 255)
         print("Shape e:", e)
         print("Position t:", t * 255)

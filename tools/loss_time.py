@@ -6,7 +6,13 @@ bench shapes; one JSON line.  Environment knobs of libsqr's A/B builds pass thro
 times the LeastSquares loss instead, forward + backward at B = 64, R = 64, 256^2 on CUDA tensors: the
 HIP kernel path (eagerly, host clock around a device synchronise, and per call inside a replayed graph)
 against the plain-torch path (the reference's per-image code, which cannot be captured: every
-torch.where waits for the device)."""
+torch.where waits for the device).
+
+    python tools/loss_time.py lm
+
+times the Levenberg-Marquardt refinement at the same shapes: one normal-equations call and a 10-iteration
+sqr.fit.refine_lm, each eagerly and inside a replayed graph, next to the least_squares forward + backward
+call and to sqr.fit.refine's 200 Adam steps in the same process."""
 import json
 import os
 import sys
@@ -58,9 +64,63 @@ def least_squares(dev, R=64, H=256, B=64):
             "kernel_in_graph_us": round(bench.time_loss_call(crit, img, B, dev, reps=10) * 1e3, 2)}
 
 
+def _graph_us(fn, reps=20):
+    """fn() captured once in a graph; device time per replay (events around `reps` replays)."""
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    g.replay()
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(reps):
+        g.replay()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / reps
+
+
+def lm(dev, R=64, H=256, B=64):
+    """One normal-equations call and a 10-iteration refine_lm, eagerly and inside a graph, next to the
+    least_squares forward + backward call and to refine's 200 Adam steps (eager: it cannot be shorter
+    than its 200 x ~8 launches), at the shapes of the leastsquares mode."""
+    from sqr import fit
+    p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
+    img = losses.implicit_render(p, H, 1.5, 260).unsqueeze(1).contiguous()
+    torch.manual_seed(0)
+    pred = (p + 0.02 * torch.randn_like(p)).contiguous()
+    gpred = pred.clone().requires_grad_(True)
+    crit = classes.LeastSquares(R, dev)
+
+    def fwd_bwd():
+        gpred.grad = None
+        crit(img, gpred).backward()
+
+    res = {"shape": "R%d_H%d_B%d" % (R, H, B),
+           "normal_eq_eager_ms": round(_eager_ms(lambda: losses.least_squares_normal_eq(img, pred, R)), 4),
+           "normal_eq_in_graph_us": round(_graph_us(lambda: losses.least_squares_normal_eq(img, pred, R)), 2),
+           "least_squares_fwd_bwd_eager_ms": round(_eager_ms(fwd_bwd), 4),
+           "least_squares_fwd_bwd_in_graph_us": round(bench.time_loss_call(crit, img, B, dev, reps=10) * 1e3, 2),
+           "refine_lm_10_eager_ms": round(_eager_ms(lambda: fit.refine_lm(img, pred, iters=10, render_size=R)), 4),
+           "refine_lm_10_in_graph_us": round(_graph_us(lambda: fit.refine_lm(img, pred, iters=10, render_size=R)), 2),
+           "refine_adam_200_eager_ms": round(_eager_ms(lambda: fit.refine(img, pred, steps=200, render_size=R),
+                                                       warmup=1, reps=3), 3)}
+    _, before, after_lm = fit.refine_lm(img, pred, iters=10, render_size=R)
+    _, _, after_adam = fit.refine(img, pred, steps=200, render_size=R)
+    res["energy_mean"] = {"start_projected": before.mean().item(), "lm_10": after_lm.mean().item(),
+                          "adam_200": after_adam.mean().item()}
+    return res
+
+
 def main():
     dev = torch.device("cuda", 0)
     out = {"env": {k: v for k, v in os.environ.items() if k.startswith("SQR_")}}
+    if sys.argv[1:] == ["lm"]:
+        out["lm"] = lm(dev)
+        print(json.dumps(out))
+        return
     if sys.argv[1:] == ["leastsquares"]:
         out["leastsquares"] = least_squares(dev)
         print(json.dumps(out))
