@@ -16,6 +16,8 @@
  *                              preprocess_sq :224-230, depth_projection :232-282, __call__ :284-295)
  *                              + its autograd backward (analytic here)
  *   sqr_implicit_render        torch/classes.py:232-282  ImplicitLoss.depth_projection (forward only)
+ *   sqr_scan_render            no counterpart in torch/: the `data/scanner` binary behind helpers.py:27-39
+ *                              (the hard orthographic depth map the datasets' images are)
  *   sqr_explicit_loss_fwd_bwd  torch/classes.py:109-201  ExplicitLoss (occupancy :138-189, __call__ :191-201)
  *   sqr_least_squares_fwd_bwd  torch/classes.py:297-371  LeastSquares (energy_function :318-356, __call__
  *                              :358-371) + its autograd backward (analytic here)
@@ -108,6 +110,17 @@ int sqr_loss_grad_scale(const float* grad, const double* gout, long long n, floa
 /* depth_projection only: images [B,R,R] f32 in the reference's image orientation (row = R-1-y, col = x). */
 int sqr_implicit_render(const float* params, int B, int R, float tau, float sharpness, float* images,
                         void* stream);
+
+/* Scanner-style hard depth images: images [B,S,S] f32 in the same grid and orientation as
+ * sqr_implicit_render.  Pixel (r, c) looks down the ray x = c / (S - 1), y = (S - 1 - r) / (S - 1) and holds
+ * z_top, the largest z with F(x, y, z) <= 1: 0 where the ray misses the body or z_top <= 0, else z_top clamped
+ * to [0, 1].  params [B,12] f32 are clamped as for the losses (a in [.05,1], e in [.1,1], t in [0,1]); the
+ * quaternion is NORMALISED (helpers.quat2mat, as the scanner is fed) and there is no zero fix.  levels > 0
+ * quantises to floor(levels z) / levels (255: the scanner's 8-bit image / 255); levels = 0 keeps the
+ * continuous depth.  A sample with a non-finite parameter or an all-zero quaternion renders as zeros.
+ * One thread per pixel, no atomics: bitwise reproducible.  1 <= B <= 65535, 2 <= S <= 8192,
+ * 0 <= levels <= 2^24. */
+int sqr_scan_render(const float* params, int B, int S, int levels, float* images, void* stream);
 
 size_t sqr_explicit_loss_workspace_bytes(int B, int R);
 

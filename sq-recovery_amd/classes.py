@@ -133,14 +133,21 @@ class SyntheticDataset(data.Dataset):
     min(size, 64)^2 by the host renderer and nearest-upsampled — plumbing data for config 1).
     Same interface (set_mode / __len__ / __getitem__ -> (X [1,H,W], y [12])); items are device
     tensors, so use a DataLoader with num_workers=0 (or batches()).
+    render="scanner" fills the images with the scanner's hard depth maps instead (scan_render at full size,
+    256 levels / 255: what the reference's datasets hold; HIP kernel on the GPU, sqr/cpu.py on the host).
     Rank r of a data-parallel job passes seed + r to get its own shard."""
 
-    def __init__(self, n, device, train_split=0.9, size=256, seed=0, tau=1.5, sharpness=260):
+    def __init__(self, n, device, train_split=0.9, size=256, seed=0, tau=1.5, sharpness=260, render="soft"):
+        if render not in ("soft", "scanner"):
+            raise ValueError("render must be 'soft' or 'scanner', got %r" % (render,))
         rng = np.random.default_rng(seed)
         self.labels = torch.tensor(sample_sq_params(rng, n), device=device)
         self.images = torch.empty((n, 1, size, size), dtype=torch.float32, device=device)
         for i in range(0, n, 256):  # bounded render batches
-            if self.labels.is_cuda:
+            if render == "scanner":
+                scan = _L.scan_render if self.labels.is_cuda else _cpu.scan_render
+                self.images[i:i + 256, 0] = scan(self.labels[i:i + 256], size, 255).to(torch.float32)
+            elif self.labels.is_cuda:
                 self.images[i:i + 256, 0] = _L.implicit_render(self.labels[i:i + 256], size, tau, sharpness)
             else:
                 r = _cpu.render(self.labels[i:i + 256], min(size, 64), tau, sharpness).float().unsqueeze(1)

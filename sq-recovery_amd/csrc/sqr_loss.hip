@@ -1,6 +1,6 @@
 // Fused superquadric losses for gfx950: ImplicitLoss (render + MAE + analytic gradient),
-// ExplicitLoss (occupancy MSE + gradient), LeastSquares (point-set energy + gradient) and IoUAccuracy
-// counts.
+// ExplicitLoss (occupancy MSE + gradient), LeastSquares (point-set energy + gradient), IoUAccuracy
+// counts and the scanner-style hard depth render (scan_render_kernel).
 //
 // Reference algorithm (timoblak/sq-recovery, torch/):
 //   grid               classes.py:217-222 (linspace, exact 0 -> 1e-4), :121-126 (arange, R+1 points)
@@ -553,6 +553,125 @@ __global__ void __launch_bounds__(NT) implicit_render_kernel(const float* __rest
     sumOM += 1.f - fexp2(ntau * S);
   }
   images[((size_t)b * R + r) * R + c] = sumOM / (float)R;
+}
+
+// -------------------------------------------------------------------------- scanner depth render
+// The hard depth map of the reference's `data/scanner` binary (helpers.py:27-39; no counterpart in torch/):
+// pixel (r, c) of an S x S image looks down the ray x = c / (S - 1), y = (S - 1 - r) / (S - 1) and holds z_top,
+// the largest z with F <= 1 (0 on a miss or where z_top <= 0, else clamped to [0, 1]).  No zero fix, and the
+// quaternion is normalised (helpers.quat2mat).  Along the ray u_i = al_i + be_i z (ray_u) and
+// f = (|u0|^(2/e2) + |u1|^(2/e2))^(e2/e1) + |u2|^(2/e1) = F^(1/e1) is convex in z for e <= 1: the inside set is
+// one interval within the slab |u_i| <= 1.  Two bisections with fixed budgets (sqr/cpu.py's scan_render is the
+// same procedure): on the sign of df/dz for a point with f <= 1, left as soon as no lane of the wave still
+// looks for one, then on log2 f <= 0 between that point and the slab's upper end.  A wave is an 8 x 8 pixel
+// tile, so most waves are all miss (no evaluation at all) or all interior.  One thread per pixel, a pure map.
+constexpr float kScanZLo = -3.f, kScanZHi = 4.f;  // a >= 0.05, t in [0, 1], |u| <= 1: z in [-sqrt 3, 1 + sqrt 3]
+constexpr int kScanMinIters = 26, kScanRootIters = 28;  // a bracket at most 7 wide down to an ulp of z
+
+// log2 f at depth z and a value with the sign of df/dz.  A term with u_i = 0 is an exact 0: log2 = -inf, and
+// lse2 is not asked for log2(0 + 0) (its max - min would be inf - inf)
+__device__ __forceinline__ float scan_eval(const SQ& s, const RayU& r, float z, float& dsign) {
+  const float u0 = fmaf(r.be[0], z, r.al[0]), u1 = fmaf(r.be[1], z, r.al[1]), u2 = fmaf(r.be[2], z, r.al[2]);
+  const float lA = flog2(fabsf(u0)) * r.i2e2, lB = flog2(fabsf(u1)) * r.i2e2, lC = flog2(fabsf(u2)) * r.i2e1;
+  float sA, sB, sE, sC;
+  const bool noAB = fmaxf(lA, lB) == -INFINITY;
+  const float l1 = lse2(lA, lB, &sA, &sB);
+  const float lE = noAB ? -INFINITY : s.r21 * l1;
+  const bool none = fmaxf(lE, lC) == -INFINITY;
+  const float l2 = lse2(lE, lC, &sE, &sC);
+  // d ln f / dz = (2 / e1) (sE (sA be0 / u0 + sB be1 / u1) + sC be2 / u2); a share of 0 over a u of 0 is 0
+  constexpr float tiny = 1e-30f;
+  const float g0 = (!noAB && fabsf(u0) > tiny) ? sA * r.be[0] * frcp(u0) : 0.f;
+  const float g1 = (!noAB && fabsf(u1) > tiny) ? sB * r.be[1] * frcp(u1) : 0.f;
+  const float g2 = (!none && fabsf(u2) > tiny) ? sC * r.be[2] * frcp(u2) : 0.f;
+  dsign = none ? 0.f : fmaf(sE, g0 + g1, g2);
+  return none ? -INFINITY : l2;
+}
+
+// grid: (tiles of 16 x 16 pixels, B); 256 threads, wave w of a block is the 8 x 8 tile (w & 1, w >> 1)
+__global__ void __launch_bounds__(256) scan_render_kernel(const float* __restrict__ params, int S, float levels,
+                                                          float* __restrict__ images) {
+  const int b = blockIdx.y;
+  const int tiles = (S + 15) >> 4;
+  const int ty = blockIdx.x / tiles, tx = blockIdx.x - ty * tiles;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int r = ty * 16 + (wid >> 1) * 8 + (lane >> 3), c = tx * 16 + (wid & 1) * 8 + (lane & 7);
+  const bool active = r < S && c < S;
+  // the sample: a non-finite parameter or an all-zero quaternion renders as zeros
+  float raw[12];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    raw[i] = params[12 * (size_t)b + i];
+    ok = ok && isfinite(raw[i]);
+  }
+  const float qmax = fmaxf(fmaxf(fabsf(raw[8]), fabsf(raw[9])), fmaxf(fabsf(raw[10]), fabsf(raw[11])));
+  ok = ok && qmax > 0.f;
+  if (!ok) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) raw[i] = 0.5f;
+    raw[8] = raw[9] = raw[10] = 0.f;
+    raw[11] = 1.f;
+  } else {
+    // q / |q|, scaled by its largest component first (the squares cannot over- or underflow)
+    const float is = 1.f / qmax;
+    const float q0 = raw[8] * is, q1 = raw[9] * is, q2 = raw[10] * is, q3 = raw[11] * is;
+    const float in = 1.f / sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    raw[8] = q0 * in; raw[9] = q1 * in; raw[10] = q2 * in; raw[11] = q3 * in;
+  }
+  SQ s;
+  sq_load(raw, s);
+  const float den = (float)(S - 1);
+  const float dx = (float)c / den - s.t[0], dy = (float)(S - 1 - r) / den - s.t[1];
+  RayU ru;
+  ray_u(s, dx, dy, ru);
+  // slab |u_i| <= 1: [z0, z1], or a miss.  be_i = 0 (axis-aligned rotations): nothing to divide by, the
+  // ray is inside that slab everywhere (|al_i| <= 1) or nowhere
+  float z0 = kScanZLo, z1 = kScanZHi;
+  bool hit = active && ok;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const bool flat = ru.be[i] == 0.f;
+    const float ib = 1.f / (flat ? 1.f : ru.be[i]);
+    const float za = (-1.f - ru.al[i]) * ib, zb = (1.f - ru.al[i]) * ib;
+    hit = hit && !(flat && fabsf(ru.al[i]) > 1.f);
+    z0 = flat ? z0 : fmaxf(z0, fminf(za, zb));
+    z1 = flat ? z1 : fminf(z1, fmaxf(za, zb));
+  }
+  hit = hit && z0 <= z1;
+  float depth = 0.f;
+  if (__any(hit)) {
+    // a point with f <= 1: bisection on the sign of df/dz towards the minimum of f along the ray
+    float lo = z0, hi = z1, zin = 0.f;
+    bool found = false;
+    for (int it = 0; it < kScanMinIters; ++it) {
+      if (!__any(hit && !found)) break;
+      const float mid = 0.5f * (lo + hi);
+      float d;
+      const float lf = scan_eval(s, ru, mid, d);
+      if (!found && lf <= 0.f) {
+        found = true;
+        zin = mid;
+      }
+      if (d > 0.f) hi = mid; else lo = mid;  // f rises: the minimum lies below
+    }
+    found = found && hit;
+    if (__any(found)) {
+      lo = zin;
+      hi = z1;
+      for (int it = 0; it < kScanRootIters; ++it) {  // f(lo) <= 1 < f(hi): the upper root of f = 1
+        const float mid = 0.5f * (lo + hi);
+        float d;
+        const bool inside = scan_eval(s, ru, mid, d) <= 0.f;
+        lo = inside ? mid : lo;
+        hi = inside ? hi : mid;
+      }
+      const float zt = 0.5f * (lo + hi);
+      if (found && zt > 0.f) depth = fminf(zt, 1.f);
+      if (levels > 0.f) depth = floorf(levels * depth) / levels;
+    }
+  }
+  if (active) images[((size_t)b * S + r) * S + c] = depth;
 }
 
 // -------------------------------------------------------------------------- ExplicitLoss
@@ -1130,6 +1249,18 @@ extern "C" int sqr_implicit_render(const float* params, int B, int R, float tau,
   hipLaunchKernelGGL((implicit_render_kernel<256>), dim3(nblk, B), dim3(256), 0, as_stream(stream), params,
                      R, tau, sharpness, images);
   SQR_HIP_LAUNCH_CHECK("implicit_render_kernel");
+  return SQR_OK;
+}
+
+extern "C" int sqr_scan_render(const float* params, int B, int S, int levels, float* images, void* stream) {
+  SQR_CHECK_ARG(B >= 1 && B <= 65535, "scan_render: B=%d out of range [1,65535]", B);
+  SQR_CHECK_ARG(S >= 2 && S <= 8192, "scan_render: S=%d out of range [2,8192]", S);
+  SQR_CHECK_ARG(levels >= 0 && levels <= (1 << 24), "scan_render: levels=%d out of range [0,2^24]", levels);
+  SQR_CHECK_ARG(params && images, "scan_render: null pointer");
+  const int tiles = (S + 15) / 16;
+  hipLaunchKernelGGL(scan_render_kernel, dim3(tiles * tiles, B), dim3(256), 0, as_stream(stream), params, S,
+                     (float)levels, images);
+  SQR_HIP_LAUNCH_CHECK("scan_render_kernel");
   return SQR_OK;
 }
 

@@ -1,5 +1,5 @@
-"""Drop-in for torch/helpers.py (timoblak/sq-recovery): checkpoints, label parsing and scanner
-command lines — the parts train.py / test.py use.  The reference's plotting and autograd-debug
+"""Drop-in for torch/helpers.py (timoblak/sq-recovery): checkpoints, label parsing, BMP reading and
+writing, and scanner command lines — the parts train.py / test.py use.  The reference's plotting and autograd-debug
 utilities (plot_render, plot_points, gray_to_jet, plot_grad_flow, getBack, slerp, randquat;
 helpers.py:108-320) are out of scope and not restated.
 
@@ -131,6 +131,24 @@ def read_image_gray(path):
     else:
         img = np.clip(np.rint(0.114 * bgr[..., 0] + 0.587 * bgr[..., 1] + 0.299 * bgr[..., 2]), 0, 255).astype(np.uint8)
     return np.ascontiguousarray(img[::-1] if h > 0 else img)
+
+
+def write_image_gray(path, img_u8):
+    """Write a uint8 [H,W] image as the scanner's 24-bit bottom-up BMP (gray in B, G and R);
+    read_image_gray reads it back identically."""
+    img = np.ascontiguousarray(img_u8)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError("write_image_gray: expected a uint8 [H,W] image, got %s %s" % (img.dtype, img.shape))
+    h, w = img.shape
+    stride = (w * 3 + 3) & ~3
+    rows = np.zeros((h, stride), np.uint8)
+    rows[:, :w * 3] = np.repeat(img[::-1], 3, axis=1)
+    u32 = lambda v: int(v).to_bytes(4, "little")  # noqa: E731
+    header = (b"BM" + u32(54 + rows.size) + u32(0) + u32(54)  # file header: size, reserved, pixel offset
+              + u32(40) + u32(w) + u32(h) + (1).to_bytes(2, "little") + (24).to_bytes(2, "little")
+              + u32(0) + u32(rows.size) + u32(2835) + u32(2835) + u32(0) + u32(0))
+    with open(path, "wb") as f:
+        f.write(header + rows.tobytes())
 
 
 def change_lr(opt, lr):

@@ -211,6 +211,19 @@ def implicit_render(params, R, tau=1.0, sharpness=100.0):
     return out
 
 
+def scan_render(params, size=256, levels=255):
+    """Scanner-style hard depth images [B,size,size] float32 in [0, 1] (sqr_scan_render: the largest z with
+    F <= 1 per pixel, quantised to floor(levels z) / levels; levels = 0: continuous).  No autograd."""
+    _require_cuda(params)
+    if params.dim() != 2 or params.shape[1] != 12:
+        raise ValueError("params must be [B,12], got %s" % (tuple(params.shape),))
+    p = params.detach().to(torch.float32).contiguous()
+    out = torch.empty(p.shape[0], int(size), int(size), dtype=torch.float32, device=p.device)
+    check(lib().sqr_scan_render(ptr(p), p.shape[0], int(size), int(levels), ptr(out), stream_ptr(p.device)),
+          "sqr_scan_render")
+    return out
+
+
 def iou_counts(p_true, p_pred, R):
     """[B,2] int64 (intersection, union) voxel counts of IoUAccuracy (classes.py:394-447).  The
     kernel works in float64 like the reference; float64 parameters (visu.py) are used as given."""

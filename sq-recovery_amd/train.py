@@ -20,7 +20,8 @@ MI355X-specific:
     with backward, captured in the step graph below as in bench.py), each rank trains on its own
     contiguous shard (sqr.dist.shard), rank 0 logs and writes checkpoints (un-prefixed state-dict
     keys); --dp-rehearsal runs that path on one GPU with a world-1 communicator;
-  * --synthetic N trains on N rendered SQ images (no dataset files needed); otherwise the
+  * --synthetic N trains on N rendered SQ images (no dataset files needed; --synthetic-render scanner: the
+    scanner's hard depth maps, sqr_scan_render, instead of the soft ImplicitLoss render); otherwise the
     reference's H5Dataset(dataset_location, parse_csv(labels), 0.9) is used (needs h5py);
   * on CUDA the whole training step (forward, loss, backward, all-reduce, Adam / loss scaler) is
     captured in one HIP graph and replayed per batch (sqr.step.CapturedStep: static batch buffers,
@@ -56,6 +57,8 @@ def parse_args(argv=None):
     ap.add_argument("--dataset-location", default="../data/data/")
     ap.add_argument("--labels", default="../data/annotations/data_labels.csv")
     ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images instead of the h5 set")
+    ap.add_argument("--synthetic-render", default="soft", choices=("soft", "scanner"),
+                    help="--synthetic images: the soft ImplicitLoss render, or the scanner's hard depth maps")
     ap.add_argument("--model-location", default="trained_models/model_full.pt")
     ap.add_argument("--epochs", type=int, default=20000)
     ap.add_argument("--batch-size", type=int, default=32, help="per-GPU batch")
@@ -112,7 +115,7 @@ def main(argv=None):
 
     if args.synthetic:
         # every rank renders the same set and trains on its own shard
-        dataset = SyntheticDataset(args.synthetic, device, train_split=0.9, seed=0)
+        dataset = SyntheticDataset(args.synthetic, device, train_split=0.9, seed=0, render=args.synthetic_render)
     else:
         dataset = H5Dataset(args.dataset_location, parse_csv(args.labels), train_split=0.9, dataset_file="dataset.h5")
 

@@ -12,7 +12,13 @@ torch.where waits for the device).
 
 times the Levenberg-Marquardt refinement at the same shapes: one normal-equations call and a 10-iteration
 sqr.fit.refine_lm, each eagerly and inside a replayed graph, next to the least_squares forward + backward
-call and to sqr.fit.refine's 200 Adam steps in the same process."""
+call and to sqr.fit.refine's 200 Adam steps in the same process.
+
+    python tools/loss_time.py scan
+
+times the scanner-style depth render (sqr_scan_render) at B = 256, S = 256, eagerly and inside a replayed
+graph, next to implicit_render at the same B and S (the render it stands beside in SyntheticDataset; the two
+produce different images) and to the float64 host renderer on 16 threads over 16 of the images."""
 import json
 import os
 import sys
@@ -114,9 +120,36 @@ def lm(dev, R=64, H=256, B=64):
     return res
 
 
+def scan(dev, S=256, B=256, host_images=16):
+    from sqr import cpu
+    p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
+    img = losses.scan_render(p, S, 255)
+    res = {"shape": "S%d_B%d" % (S, B), "foreground_share": round(float((img > 0).float().mean()), 4),
+           # (windows of ~0.2 s and more: 400 calls of the half-millisecond render, 40 of the soft one)
+           "scan_render_eager_ms": round(_eager_ms(lambda: losses.scan_render(p, S, 255), reps=400), 4),
+           "scan_render_in_graph_us": round(_graph_us(lambda: losses.scan_render(p, S, 255), reps=400), 2),
+           "implicit_render_eager_ms": round(_eager_ms(lambda: losses.implicit_render(p, S, 1.5, 260), reps=40), 4),
+           "implicit_render_in_graph_us": round(_graph_us(lambda: losses.implicit_render(p, S, 1.5, 260), reps=40),
+                                                2)}
+    threads = torch.get_num_threads()
+    torch.set_num_threads(16)
+    ph = p[:host_images].cpu()
+    cpu.scan_render(ph[:1], S, 255)
+    t0 = time.perf_counter()
+    cpu.scan_render(ph, S, 255)
+    res["host_float64_ms_per_%d_images" % host_images] = round((time.perf_counter() - t0) * 1e3, 1)
+    res["host_threads"] = 16
+    torch.set_num_threads(threads)
+    return res
+
+
 def main():
     dev = torch.device("cuda", 0)
     out = {"env": {k: v for k, v in os.environ.items() if k.startswith("SQR_")}}
+    if sys.argv[1:] == ["scan"]:
+        out["scan"] = scan(dev)
+        print(json.dumps(out))
+        return
     if sys.argv[1:] == ["lm"]:
         out["lm"] = lm(dev)
         print(json.dumps(out))
