@@ -24,6 +24,9 @@
  *   sqr_least_squares_normal_eq, sqr_lsq_lm_step, sqr_lsq_lm_refine
  *                              no counterpart: Levenberg-Marquardt on the residuals behind LeastSquares'
  *                              energy_function (classes.py:318-356), Solina & Bajcsy's own method
+ *   sqr_lsq_starts, sqr_lsq_select, sqr_lsq_recover
+ *                              no counterpart: that method's start from the image's points alone (centre of
+ *                              gravity, principal axes, extents) and the best of three refined starts
  *   sqr_iou_counts             torch/classes.py:374-447  IoUAccuracy (ins_outs :394-426, __call__ :428-447)
  *   sqr_conv2d_fwd / _bwd_data / _bwd_weight
  *                              torch.nn.Conv2d as used by torchvision resnet18 inside ResNetSQ
@@ -200,6 +203,57 @@ size_t sqr_lsq_lm_refine_workspace_bytes(int B, int R);
 int sqr_lsq_lm_refine(const float* params_in, const float* target, int B, int H, int W, int R, int iters,
                       double lambda0, double up, double down, float* params_out, double* energy_before,
                       double* energy_after, int* accepted, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_lsq_starts for B samples at render size R. */
+size_t sqr_lsq_starts_workspace_bytes(int B, int R);
+
+/* Solina & Bajcsy's starts of the recovery from the points of each image alone (the points of
+ * sqr_least_squares_fwd_bwd: same pixel rule, same resize arithmetic; a NaN pixel does not count), four
+ * launches on `stream`, float64, bitwise reproducible, a sample's outputs independent of the batch:
+ *   count       [B] i32     : the number of points n
+ *   centroid    [B,3] f64   : c = sum p / n
+ *   eigenvalues [B,3] f64   : of the covariance C = sum p p^T / n - c c^T, ascending (cyclic Jacobi)
+ *   frame       [B,3,3] f64 : V, row-major, the eigenvectors its columns, a proper rotation (det +1).  Sign
+ *                             rule: the component of the largest magnitude (the first on a tie) is negative in
+ *                             column 0 and positive in column 1, column 2 = column 0 x column 1
+ *   starts      [3,B,12] f32: start k has the local axes M_k = columns (k, k+1, k+2 mod 3) of V: a = half the
+ *                             extents (max - min of V^T p over the points) in that order, clamped into
+ *                             [0.05,1]; e = (e0, e0); t = M_k (midpoint of the extents), clamped into [0,1];
+ *                             q = the xyzw quaternion with mat_from_quaternion(q) = M_k (branch on the largest
+ *                             of trace, m00, m11, m22)
+ * Debugging output, documented so that the moments can be checked on their own (no caller needs it, and
+ * sqr_lsq_recover's workspace makes no such promise): on return the workspace begins with the moments' per-block
+ * partials [B][ceil(R^2 / 256)][10] f64: the sums of
+ * xx xy xz x yy yz y zz z 1 over each block of 256 resized pixels (added in block order by the frame launch),
+ * followed by the extents' partials [B][blocks][6] f64 (minima, then maxima).
+ * An image without points (or with moments that are not finite) gets a = 0.05, e = e0, t = 0.5,
+ * q = (0,0,0,1) in all three starts; without points count = 0, centroid = eigenvalues = 0 and V = I.
+ * 1 <= B <= 65535, 1 <= R <= 1024, H,W >= 1, 0.1 <= e0 <= 1; otherwise, or with a short workspace,
+ * SQR_E_INVALID_ARG and nothing is launched. */
+int sqr_lsq_starts(const float* target, int B, int H, int W, int R, float e0, float* starts, int* count,
+                   double* centroid, double* eigenvalues, double* frame, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* Per sample the best of K candidates: out_index [B] i32 = the index of the lowest of energy [K,B] f64 (the
+ * lowest index on a tie; NaN never wins; all NaN: 0), out_params [B,12] f32 = params [K,B,12] at that index,
+ * out_energy [B] f64 its energy.  One launch.  B,K >= 1. */
+int sqr_lsq_select(int B, int K, const float* params, const double* energy, float* out_params, double* out_energy,
+                   int* out_index, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_lsq_recover for B samples at render size R. */
+size_t sqr_lsq_recover_workspace_bytes(int B, int R);
+
+/* Recovery of B superquadrics from their depth images alone: sqr_lsq_starts, then sqr_lsq_lm_refine from
+ * each of the three starts (one after the other on `stream`, in one workspace region), then sqr_lsq_select
+ * on the three final energies.  No host wait, no allocation: capturable.
+ *   params_out [B,12] f32, energy_out [B] f64, index_out [B] i32 : the winner, its energy, its start
+ *   all_params [3,B,12] f32, all_before [3,B] f64, all_after [3,B] f64, all_accepted [3,B] i32 : every
+ *   start's refined parameters, energy at the projected start, final energy and accepted steps.
+ * Arguments as sqr_lsq_starts and sqr_lsq_lm_refine; SQR_E_INVALID_ARG (nothing launched) as there. */
+int sqr_lsq_recover(const float* target, int B, int H, int W, int R, int iters, float e0, double lambda0, double up,
+                    double down, float* params_out, double* energy_out, int* index_out, float* all_params,
+                    double* all_before, double* all_after, int* all_accepted, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* IoUAccuracy(R): per-sample voxel counts [B,2] int64 = (|in_true & in_pred|, |in_true | in_pred|),
  * computed in float64 like the reference. */

@@ -1,6 +1,7 @@
 // Fused superquadric losses for gfx950: ImplicitLoss (render + MAE + analytic gradient),
 // ExplicitLoss (occupancy MSE + gradient), LeastSquares (point-set energy + gradient), IoUAccuracy
-// counts and the scanner-style hard depth render (scan_render_kernel).
+// counts, the scanner-style hard depth render (scan_render_kernel) and the classical recovery's starts and
+// selection around the Levenberg-Marquardt loop (lsq_moments_kernel .. lsq_select_kernel).
 //
 // Reference algorithm (timoblak/sq-recovery, torch/):
 //   grid               classes.py:217-222 (linspace, exact 0 -> 1e-4), :121-126 (arange, R+1 points)
@@ -1086,6 +1087,300 @@ __global__ void __launch_bounds__(64) lm_step_kernel(int B, int accept, int solv
   lambda[b] = lam;
 }
 
+// -------------------------------------------------------------------------- LeastSquares starts (recovery)
+// Solina & Bajcsy's start of the recovery, from the image's points alone (no counterpart in torch/): the
+// centre of gravity and the principal axes of the points give position and orientation, the extents along
+// those axes the sizes, an ellipsoid (e = e0) the shape; the three cyclic permutations of the axes are the
+// three starts that sqr_lsq_recover refines.  Four launches, every one with least_squares_kernel's point
+// rule: lsq_moments_kernel (n, sum p, sum p p^T per block), lsq_frame_kernel (centroid, covariance,
+// eigen-frame per sample), lsq_extents_kernel (min / max of V^T p per block), lsq_starts_kernel (one thread
+// per sample and start).  lsq_select_kernel picks the refined start of the lowest energy.
+constexpr int kMomN = 10;         // upper triangle of the Gram matrix of the rows [x y z 1]: xx xy xz x yy yz y zz z n
+constexpr int kJacobiSweeps = 8;  // cyclic Jacobi on a 3 x 3 converges quadratically: 4-5 sweeps reach an ulp
+
+// the point (c / R, 1 - r / R, z) of resized pixel `pix` of image b and whether it counts (z > 0: false for
+// NaN); the resize arithmetic of least_squares_kernel
+__device__ __forceinline__ bool lsq_point(const float* __restrict__ target, int b, int H, int W, int R, int pix,
+                                          float& x, float& y, float& z) {
+  x = y = z = 0.f;
+  if (pix >= R * R) return false;
+  const int r = pix / R, c = pix - r * R;
+  const float sh = (float)H / (float)R, sw = (float)W / (float)R;
+  const int sr = min((int)floorf((float)r * sh), H - 1);
+  const int sc = min((int)floorf((float)c * sw), W - 1);
+  z = target[((size_t)b * H + sr) * W + sc];
+  x = (float)c / (float)R;
+  y = 1.f - (float)r / (float)R;
+  return z > 0.f;
+}
+
+// grid: (blocks_per_sample, B); one thread per resized pixel.  partials: [B][nblk][kMomN] float64.  The
+// products of two floats are exact in float64; lanes are summed by DPP (wave_sum_d), waves in order, as
+// least_squares_kernel does, so the sums are bitwise defined.  A pixel that does not count is a zero row.
+template <int NT>
+__global__ void __launch_bounds__(NT) lsq_moments_kernel(const float* __restrict__ target, int H, int W, int R,
+                                                         double* __restrict__ partials) {
+  __shared__ double red[(NT / 64) * kMomN];
+  const int b = blockIdx.y;
+  float fx, fy, fz;
+  const bool on = lsq_point(target, b, H, W, R, blockIdx.x * NT + threadIdx.x, fx, fy, fz);
+  const double x = on ? (double)fx : 0.0, y = on ? (double)fy : 0.0, z = on ? (double)fz : 0.0;
+  const double one = on ? 1.0 : 0.0;
+  const double vals[kMomN] = {x * x, x * y, x * z, x, y * y, y * z, y, z * z, z, one};
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < kMomN; ++i) {
+    const double v = wave_sum_d(vals[i]);
+    if (lane == 0) red[wid * kMomN + i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kMomN) {
+    double acc = 0.0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) acc += red[w * kMomN + threadIdx.x];
+    partials[((size_t)b * gridDim.x + blockIdx.x) * kMomN + threadIdx.x] = acc;
+  }
+}
+
+// one Jacobi rotation of the symmetric 3 x 3 in the (p, q) plane, r the third index: a_pq -> 0, the
+// eigenvector columns p and q of V rotated along (a proper rotation: det V stays +1)
+__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq,
+                                              double& v0p, double& v0q, double& v1p, double& v1q, double& v2p,
+                                              double& v2q) {
+  const bool go = apq != 0.0;
+  const double theta = (aqq - app) / (2.0 * (go ? apq : 1.0));
+  // the smaller root of t^2 + 2 theta t - 1 = 0; theta^2 = inf gives t = 0
+  double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  t = go ? t : 0.0;
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app -= t * apq;
+  aqq += t * apq;
+  apq = go ? 0.0 : apq;
+  const double rp = arp, rq = arq;
+  arp = c * rp - s * rq;
+  arq = s * rp + c * rq;
+  const double a0 = v0p, b0 = v0q, a1 = v1p, b1 = v1q, a2 = v2p, b2 = v2q;
+  v0p = c * a0 - s * b0; v0q = s * a0 + c * b0;
+  v1p = c * a1 - s * b1; v1q = s * a1 + c * b1;
+  v2p = c * a2 - s * b2; v2q = s * a2 + c * b2;
+}
+
+// the column (x, y, z) with its component of the largest magnitude (the first one on a tie) given the sign of
+// `sign`
+__device__ __forceinline__ void frame_sign(double& x, double& y, double& z, double sign) {
+  const double ax = fabs(x), ay = fabs(y), az = fabs(z);
+  const double lead = (ax >= ay && ax >= az) ? x : (ay >= az ? y : z);
+  if (lead * sign < 0.0) {
+    x = -x;
+    y = -y;
+    z = -z;
+  }
+}
+
+// One thread per sample, float64: the blocks' moments in order, n, the centroid c = sum p / n, the covariance
+// C = sum p p^T / n - c c^T and its eigen-decomposition by cyclic Jacobi, kJacobiSweeps sweeps over (0,1),
+// (0,2), (1,2), fully unrolled on named scalars (registers; lm_step_kernel's lesson).  Eigenvalues ascending
+// (a three-exchange sort, columns along); sign rule: the largest-magnitude component of column 0 is made
+// negative and that of column 1 positive (frame_sign), column 2 = column 0 x column 1, so V is a proper rotation
+// and a function of C alone.  (The four sign choices are the same body, but not the same Levenberg-Marquardt
+// path: mat_from_quaternion is not normalised, so the Jacobian's radial part differs.  DESIGN.md has the four
+// outcomes on the example images.)
+// frame [B,3,3] row-major, the eigenvectors its columns.  No point: n = 0, zeros, V = I.
+__global__ void __launch_bounds__(64) lsq_frame_kernel(const double* __restrict__ partials, int B, int nblk,
+                                                       int* __restrict__ count, double* __restrict__ centroid,
+                                                       double* __restrict__ eigenvalues,
+                                                       double* __restrict__ frame) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double S[kMomN];
+#pragma unroll
+  for (int i = 0; i < kMomN; ++i) S[i] = 0.0;
+  for (int k = 0; k < nblk; ++k) {
+    const double* src = partials + ((size_t)b * nblk + k) * kMomN;
+#pragma unroll
+    for (int i = 0; i < kMomN; ++i) S[i] += src[i];
+  }
+  const double n = S[9];
+  double cx = 0.0, cy = 0.0, cz = 0.0, l0 = 0.0, l1 = 0.0, l2 = 0.0;
+  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+  if (n > 0.0) {
+    const double in = 1.0 / n;
+    cx = S[3] * in;
+    cy = S[6] * in;
+    cz = S[8] * in;
+    double a00 = S[0] * in - cx * cx, a01 = S[1] * in - cx * cy, a02 = S[2] * in - cx * cz;
+    double a11 = S[4] * in - cy * cy, a12 = S[5] * in - cy * cz, a22 = S[7] * in - cz * cz;
+#pragma unroll
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+      jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);  // (0,1), r = 2
+      jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);  // (0,2), r = 1
+      jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);  // (1,2), r = 0
+    }
+    l0 = a00;
+    l1 = a11;
+    l2 = a22;
+    auto exch = [](double& la, double& lb, double& a0, double& b0, double& a1, double& b1, double& a2, double& b2) {
+      if (la > lb) {
+        double t;
+        t = la; la = lb; lb = t;
+        t = a0; a0 = b0; b0 = t;
+        t = a1; a1 = b1; b1 = t;
+        t = a2; a2 = b2; b2 = t;
+      }
+    };
+    exch(l0, l1, v00, v01, v10, v11, v20, v21);
+    exch(l1, l2, v01, v02, v11, v12, v21, v22);
+    exch(l0, l1, v00, v01, v10, v11, v20, v21);
+    frame_sign(v00, v10, v20, -1.0);
+    frame_sign(v01, v11, v21, 1.0);
+    v02 = v10 * v21 - v20 * v11;
+    v12 = v20 * v01 - v00 * v21;
+    v22 = v00 * v11 - v10 * v01;
+  }
+  count[b] = (int)n;
+  centroid[3 * (size_t)b] = cx;
+  centroid[3 * (size_t)b + 1] = cy;
+  centroid[3 * (size_t)b + 2] = cz;
+  eigenvalues[3 * (size_t)b] = l0;
+  eigenvalues[3 * (size_t)b + 1] = l1;
+  eigenvalues[3 * (size_t)b + 2] = l2;
+  double* V = frame + 9 * (size_t)b;
+  V[0] = v00; V[1] = v01; V[2] = v02;
+  V[3] = v10; V[4] = v11; V[5] = v12;
+  V[6] = v20; V[7] = v21; V[8] = v22;
+}
+
+// grid: (blocks_per_sample, B); one thread per resized pixel, float64.  partials: [B][nblk][6] = the block's
+// minimum (0..2) and maximum (3..5) of V^T p along the three axes over its counted points (+inf / -inf where
+// it has none).  min and max do not depend on the order: any reduction is bitwise reproducible.
+template <int NT>
+__global__ void __launch_bounds__(NT) lsq_extents_kernel(const float* __restrict__ target, int H, int W, int R,
+                                                         const double* __restrict__ frame,
+                                                         double* __restrict__ partials) {
+  __shared__ double red[(NT / 64) * 6];
+  const int b = blockIdx.y;
+  const double* V = frame + 9 * (size_t)b;
+  float fx, fy, fz;
+  const bool on = lsq_point(target, b, H, W, R, blockIdx.x * NT + threadIdx.x, fx, fy, fz);
+  double v[6];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double u = V[j] * (double)fx + V[3 + j] * (double)fy + V[6 + j] * (double)fz;
+    v[j] = on ? u : (double)INFINITY;
+    v[3 + j] = on ? u : -(double)INFINITY;
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    for (int o = 32; o >= 1; o >>= 1) {
+      v[j] = fmin(v[j], __shfl_xor(v[j], o));
+      v[3 + j] = fmax(v[3 + j], __shfl_xor(v[3 + j], o));
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) red[wid * 6 + j] = v[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    double acc = red[threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < NT / 64; ++w)
+      acc = threadIdx.x < 3 ? fmin(acc, red[w * 6 + threadIdx.x]) : fmax(acc, red[w * 6 + threadIdx.x]);
+    partials[((size_t)b * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = acc;
+  }
+}
+
+// One thread per (start k, sample b), float64, stored as float32 starts [3,B,12].  M_k = the columns
+// (k, k+1, k+2 mod 3) of V: the local x, y, z axes in world coordinates, mat_from_quaternion(q) of the start
+// (a cyclic permutation: det stays +1).  a = half the extents in that order, clamped into [0.05, 1];
+// t = M_k (midpoint of the extents), clamped into [0, 1]; e = (e0, e0); q = the xyzw quaternion of M_k,
+// taken from the largest of (trace, m00, m11, m22) (the first on a tie), so that the divisor s = 4 |largest
+// component of q| >= 2.  No point, or a value that is not finite: a = 0.05, e = e0, t = 0.5, q = (0,0,0,1).
+__global__ void __launch_bounds__(64) lsq_starts_kernel(int B, int nblk, float e0, const int* __restrict__ count,
+                                                        const double* __restrict__ frame,
+                                                        const double* __restrict__ extents,
+                                                        float* __restrict__ starts) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 3 * B) return;
+  const int k = idx / B, b = idx - k * B;
+  float o[12] = {0.05f, 0.05f, 0.05f, e0, e0, 0.5f, 0.5f, 0.5f, 0.f, 0.f, 0.f, 1.f};
+  if (count[b] > 0) {
+    double M[9], half[3], mid[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int ax = k + j >= 3 ? k + j - 3 : k + j;
+      double lo = (double)INFINITY, hi = -(double)INFINITY;
+      for (int blk = 0; blk < nblk; ++blk) {
+        const double* src = extents + ((size_t)b * nblk + blk) * 6;
+        lo = fmin(lo, src[ax]);
+        hi = fmax(hi, src[3 + ax]);
+      }
+      half[j] = 0.5 * (hi - lo);
+      mid[j] = 0.5 * (hi + lo);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) M[3 * i + j] = frame[9 * (size_t)b + 3 * i + ax];
+    }
+    float c[12];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      c[i] = clampf((float)half[i], 0.05f, 1.f);
+      c[5 + i] = clampf((float)(M[3 * i] * mid[0] + M[3 * i + 1] * mid[1] + M[3 * i + 2] * mid[2]), 0.f, 1.f);
+    }
+    c[3] = c[4] = e0;
+    const double tr = M[0] + M[4] + M[8];
+    double x, y, z, w;
+    if (tr >= M[0] && tr >= M[4] && tr >= M[8]) {
+      const double s = 2.0 * sqrt(1.0 + tr);
+      w = 0.25 * s; x = (M[7] - M[5]) / s; y = (M[2] - M[6]) / s; z = (M[3] - M[1]) / s;
+    } else if (M[0] >= M[4] && M[0] >= M[8]) {
+      const double s = 2.0 * sqrt(1.0 + M[0] - M[4] - M[8]);
+      x = 0.25 * s; y = (M[1] + M[3]) / s; z = (M[2] + M[6]) / s; w = (M[7] - M[5]) / s;
+    } else if (M[4] >= M[8]) {
+      const double s = 2.0 * sqrt(1.0 + M[4] - M[0] - M[8]);
+      y = 0.25 * s; x = (M[1] + M[3]) / s; z = (M[5] + M[7]) / s; w = (M[2] - M[6]) / s;
+    } else {
+      const double s = 2.0 * sqrt(1.0 + M[8] - M[0] - M[4]);
+      z = 0.25 * s; x = (M[2] + M[6]) / s; y = (M[5] + M[7]) / s; w = (M[3] - M[1]) / s;
+    }
+    c[8] = (float)x; c[9] = (float)y; c[10] = (float)z; c[11] = (float)w;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ok = ok && isfinite(c[i]);
+    if (ok) {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) o[i] = c[i];
+    }
+  }
+  float* dst = starts + ((size_t)k * B + b) * 12;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) dst[i] = o[i];
+}
+
+// One thread per sample: the index of the lowest of the K energies [K,B] (the lowest k on a tie; NaN never
+// wins; all NaN: 0), that start's parameters [K,B,12] and energy.
+__global__ void __launch_bounds__(64) lsq_select_kernel(int B, int K, const float* __restrict__ params,
+                                                        const double* __restrict__ energy,
+                                                        float* __restrict__ out_params,
+                                                        double* __restrict__ out_energy,
+                                                        int* __restrict__ out_index) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int best = 0;
+  double be = energy[b];
+  for (int k = 1; k < K; ++k) {
+    const double e = energy[(size_t)k * B + b];
+    if (e < be || (be != be && e == e)) {
+      best = k;
+      be = e;
+    }
+  }
+  const float* src = params + ((size_t)best * B + b) * 12;
+  for (int i = 0; i < 12; ++i) out_params[12 * (size_t)b + i] = src[i];
+  out_energy[b] = be;
+  out_index[b] = best;
+}
+
 // -------------------------------------------------------------------------- IoUAccuracy (f64)
 struct SQd {
   double a[3], e1, e2, ie1, ie2, r21, tr[3], M[9];
@@ -1469,6 +1764,111 @@ extern "C" int sqr_lsq_lm_refine(const float* params_in, const float* target, in
     }
   }
   return SQR_OK;
+}
+
+static size_t starts_blocks(int R) { return ((size_t)R * R + 255) / 256; }
+
+// the moments' partials [B][nblk][kMomN], then the extents' [B][nblk][6], float64
+extern "C" size_t sqr_lsq_starts_workspace_bytes(int B, int R) {
+  if (B <= 0 || R <= 0) return 0;
+  return (size_t)B * starts_blocks(R) * (kMomN + 6) * sizeof(double);
+}
+
+// the four launches of the starts (arguments checked by the callers)
+static int launch_starts(hipStream_t st, const float* target, int B, int H, int W, int R, float e0, float* starts,
+                         int* count, double* centroid, double* eigenvalues, double* frame, double* workspace) {
+  const int nblk = (int)starts_blocks(R);
+  double* mom = workspace;
+  double* ext = mom + (size_t)B * nblk * kMomN;
+  hipLaunchKernelGGL((lsq_moments_kernel<256>), dim3(nblk, B), dim3(256), 0, st, target, H, W, R, mom);
+  SQR_HIP_LAUNCH_CHECK("lsq_moments_kernel");
+  hipLaunchKernelGGL(lsq_frame_kernel, dim3((B + 63) / 64), dim3(64), 0, st, mom, B, nblk, count, centroid,
+                     eigenvalues, frame);
+  SQR_HIP_LAUNCH_CHECK("lsq_frame_kernel");
+  hipLaunchKernelGGL((lsq_extents_kernel<256>), dim3(nblk, B), dim3(256), 0, st, target, H, W, R, frame, ext);
+  SQR_HIP_LAUNCH_CHECK("lsq_extents_kernel");
+  hipLaunchKernelGGL(lsq_starts_kernel, dim3((3 * B + 63) / 64), dim3(64), 0, st, B, nblk, e0, count, frame, ext,
+                     starts);
+  SQR_HIP_LAUNCH_CHECK("lsq_starts_kernel");
+  return SQR_OK;
+}
+
+extern "C" int sqr_lsq_starts(const float* target, int B, int H, int W, int R, float e0, float* starts, int* count,
+                              double* centroid, double* eigenvalues, double* frame, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(B >= 1 && B <= 65535, "lsq_starts: B=%d out of range [1,65535]", B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "lsq_starts: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "lsq_starts: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(e0 >= 0.1f && e0 <= 1.f, "lsq_starts: e0=%g outside [0.1,1]", (double)e0);
+  SQR_CHECK_ARG(target && starts && count && centroid && eigenvalues && frame && workspace,
+                "lsq_starts: null pointer");
+  const size_t need = sqr_lsq_starts_workspace_bytes(B, R);
+  SQR_CHECK_ARG(workspace_bytes >= need, "lsq_starts: workspace %zu < %zu bytes", workspace_bytes, need);
+  return launch_starts(as_stream(stream), target, B, H, W, R, e0, starts, count, centroid, eigenvalues, frame,
+                       (double*)workspace);
+}
+
+extern "C" int sqr_lsq_select(int B, int K, const float* params, const double* energy, float* out_params,
+                              double* out_energy, int* out_index, void* stream) {
+  SQR_CHECK_ARG(B >= 1, "lsq_select: B=%d must be >= 1", B);
+  SQR_CHECK_ARG(K >= 1, "lsq_select: K=%d must be >= 1", K);
+  SQR_CHECK_ARG(params && energy && out_params && out_energy && out_index, "lsq_select: null pointer");
+  hipLaunchKernelGGL(lsq_select_kernel, dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), B, K, params, energy,
+                     out_params, out_energy, out_index);
+  SQR_HIP_LAUNCH_CHECK("lsq_select_kernel");
+  return SQR_OK;
+}
+
+// float64 first: [centroid 3][eigenvalues 3][frame 9] per sample, then one region that the starts' partials
+// and, after them, each of the three refinements use in turn, then starts [3,B,12] f32 and count [B] i32
+constexpr size_t kRecoverDoubles = 3 + 3 + 9;
+
+static size_t recover_region_bytes(int B, int R) {
+  const size_t a = sqr_lsq_starts_workspace_bytes(B, R), b = sqr_lsq_lm_refine_workspace_bytes(B, R);
+  return a > b ? a : b;
+}
+
+extern "C" size_t sqr_lsq_recover_workspace_bytes(int B, int R) {
+  if (B <= 0 || R <= 0) return 0;
+  return (size_t)B * kRecoverDoubles * sizeof(double) + recover_region_bytes(B, R) +
+         (size_t)B * 3 * 12 * sizeof(float) + (size_t)B * sizeof(int);
+}
+
+extern "C" int sqr_lsq_recover(const float* target, int B, int H, int W, int R, int iters, float e0, double lambda0,
+                               double up, double down, float* params_out, double* energy_out, int* index_out,
+                               float* all_params, double* all_before, double* all_after, int* all_accepted,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(B >= 1 && B <= 65535, "lsq_recover: B=%d out of range [1,65535]", B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "lsq_recover: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "lsq_recover: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(iters >= 0, "lsq_recover: iters=%d must be >= 0", iters);
+  SQR_CHECK_ARG(e0 >= 0.1f && e0 <= 1.f, "lsq_recover: e0=%g outside [0.1,1]", (double)e0);
+  SQR_CHECK_ARG(lambda0 > 0.0, "lsq_recover: lambda0=%g must be > 0", lambda0);
+  SQR_CHECK_ARG(up > 1.0, "lsq_recover: up=%g must be > 1", up);
+  SQR_CHECK_ARG(down > 0.0 && down < 1.0, "lsq_recover: down=%g outside (0,1)", down);
+  SQR_CHECK_ARG(target && params_out && energy_out && index_out && all_params && all_before && all_after &&
+                    all_accepted && workspace,
+                "lsq_recover: null pointer");
+  const size_t need = sqr_lsq_recover_workspace_bytes(B, R);
+  SQR_CHECK_ARG(workspace_bytes >= need, "lsq_recover: workspace %zu < %zu bytes", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  const size_t nb = (size_t)B;
+  double* centroid = (double*)workspace;
+  double* eigenvalues = centroid + 3 * nb;
+  double* frame = eigenvalues + 3 * nb;
+  char* region = (char*)(frame + 9 * nb);
+  float* starts = (float*)(region + recover_region_bytes(B, R));
+  int* count = (int*)(starts + 3 * 12 * nb);
+  int rc = launch_starts(st, target, B, H, W, R, e0, starts, count, centroid, eigenvalues, frame, (double*)region);
+  if (rc != SQR_OK) return rc;
+  // the three refinements one after the other on the stream, each in the same region
+  for (int k = 0; k < 3; ++k) {
+    rc = sqr_lsq_lm_refine(starts + 12 * nb * k, target, B, H, W, R, iters, lambda0, up, down,
+                           all_params + 12 * nb * k, all_before + nb * k, all_after + nb * k, all_accepted + nb * k,
+                           region, sqr_lsq_lm_refine_workspace_bytes(B, R), stream);
+    if (rc != SQR_OK) return rc;
+  }
+  return sqr_lsq_select(B, 3, all_params, all_after, params_out, energy_out, index_out, stream);
 }
 
 template <typename P>

@@ -1,5 +1,6 @@
 """Point-set refinement of predicted superquadrics: descend the LeastSquares energy of the image's own
-points, with Adam (refine) or with Levenberg-Marquardt (refine_lm).
+points, with Adam (refine) or with Levenberg-Marquardt (refine_lm); and the recovery without a prediction
+(recover): the classical start from the points' moments, refined by Levenberg-Marquardt.
 
 The classical recovery (Solina & Bajcsy) fits a superquadric to the depth image's points by iterating
 on the energy a0 a1 a2 sum_points (F - 1)^2; the reference keeps that energy as its LeastSquares loss
@@ -8,12 +9,13 @@ prediction: predict, then descend.  What this promises is a lower energy — a b
 visible points — not a higher IoU against a label: the depth image shows one side of the object.
 
 Everything runs on the device (Adam: sqr_least_squares_fwd_bwd per step plus a handful of elementwise
-launches on the [B,12] tensor; LM: sqr_lsq_lm_refine, one chain of normal-equations and step kernels);
+launches on the [B,12] tensor; LM: sqr_lsq_lm_refine, one chain of normal-equations and step kernels;
+recover: sqr_lsq_recover, the starts' four launches, three such chains and a selection);
 nothing is read back inside the loop.
 """
 import torch
 
-from .losses import least_squares, lm_refine
+from .losses import least_squares, lm_refine, lsq_recover, lsq_starts
 
 
 def refine_lm(images, params, iters=10, render_size=32, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
@@ -28,6 +30,35 @@ def refine_lm(images, params, iters=10, render_size=32, lambda0=1e-3, up=10.0, d
     sample is refined on its own; no host wait, so the call can be captured in a HIP graph."""
     out, before, after, accepted = lm_refine(images, params, int(render_size), int(iters), lambda0, up, down)
     return (out, before, after, accepted) if return_info else (out, before, after)
+
+
+def recover(images, iters=30, render_size=32, e0=1.0, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
+    """images [B,1,H,W] or [B,H,W] (CUDA) -> (params [B,12] f32, energy [B] f64, start_index [B] i32), with
+    return_info also a dict: params [3,B,12], energy_before [3,B], energy_after [3,B], accepted [3,B] of every
+    start, the starts themselves [3,B,12] and the moments (count, centroid, eigenvalues, frame).
+
+    Solina & Bajcsy's recovery, no network and no label: the centre of gravity and the principal axes of the
+    image's points give position and orientation, the extents along those axes the sizes, an ellipsoid
+    (e = e0) the shape; refine_lm's iteration goes on from each of the three cyclic permutations of the axes
+    and the start that ends with the lowest energy wins (the lowest index on a tie).  The result has in-range
+    parameters and a unit quaternion, and its energy is no higher than that of any of the three projected
+    starts.  As with refine, the promise is a low energy, a good fit of the visible points, not a high IoU
+    against a label: the depth image shows one side of the object, and the lowest energy is not always the
+    best IoU.  An image without points returns the default start (a = 0.05, t = 0.5, identity rotation) with
+    energy 0.  Every sample is recovered on its own; no host wait, so the call can be captured in a HIP
+    graph.
+
+    return_info costs a second run of the starts (sqr_lsq_starts: four more short launches and five small
+    allocations): sqr_lsq_recover keeps the starts it refines in its workspace, whose layout is not part of its
+    interface.  The starts' kernels are bitwise reproducible, so the starts and moments returned are exactly
+    the ones that were refined."""
+    R = int(render_size)
+    out, energy, index, allp, before, after, accepted = lsq_recover(images, R, int(iters), e0, lambda0, up, down)
+    if not return_info:
+        return out, energy, index
+    starts, info = lsq_starts(images, R, e0)
+    info = dict(info, params=allp, energy_before=before, energy_after=after, accepted=accepted, starts=starts)
+    return out, energy, index, info
 
 
 def refine(images, params, steps=200, lr=2e-3, render_size=32, betas=(0.9, 0.999), eps=1e-8, method="adam"):

@@ -201,6 +201,83 @@ def lm_refine(target, params, R, iters, lambda0, up, down):
     return out, before, after, accepted
 
 
+def _image_only(target):
+    """The contiguous float32 [B,H,W] view of a [B,1,H,W] / [B,H,W] CUDA image batch, and B, H, W."""
+    _require_cuda(target)
+    if target.dim() == 4 and target.shape[1] == 1:
+        tgt = target[:, 0]
+    elif target.dim() == 3:
+        tgt = target
+    else:
+        raise ValueError("target must be [B,1,H,W] or [B,H,W], got %s" % (tuple(target.shape),))
+    if tgt.shape[0] < 1:
+        raise ValueError("target holds no image")
+    t = tgt.detach().to(torch.float32).contiguous()
+    return t, int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
+
+
+def lsq_starts(target, R, e0=1.0):
+    """sqr_lsq_starts -> (starts [3,B,12] f32, info): Solina & Bajcsy's three starts of the recovery from the
+    points of each image alone.  info: count [B] i32, centroid [B,3], eigenvalues [B,3] (of the points'
+    covariance, ascending) and frame [B,3,3] (the eigenvectors its columns, det +1), float64.  Start k has the
+    columns (k, k+1, k+2 mod 3) of the frame as its axes, half the points' extents along them as its sizes and
+    e = (e0, e0).  Four launches on the current stream; no host wait."""
+    t, B, H, W = _image_only(target)
+    dev = t.device
+    starts = torch.empty(3, B, 12, dtype=torch.float32, device=dev)
+    info = {"count": torch.empty(B, dtype=torch.int32, device=dev),
+            "centroid": torch.empty(B, 3, dtype=torch.float64, device=dev),
+            "eigenvalues": torch.empty(B, 3, dtype=torch.float64, device=dev),
+            "frame": torch.empty(B, 3, 3, dtype=torch.float64, device=dev)}
+    L = lib()
+    wsb = L.sqr_lsq_starts_workspace_bytes(B, int(R))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(L.sqr_lsq_starts(ptr(t), B, H, W, int(R), float(e0), ptr(starts), ptr(info["count"]), ptr(info["centroid"]),
+                           ptr(info["eigenvalues"]), ptr(info["frame"]), ptr(ws), wsb, stream_ptr(dev)),
+          "sqr_lsq_starts")
+    return starts, info
+
+
+def lsq_select(params, energy):
+    """sqr_lsq_select: params [K,B,12], energy [K,B] (CUDA) -> (params [B,12] f32, energy [B] f64, index [B]
+    i32) of the lowest energy per sample; the lowest index on a tie, NaN never wins, all NaN gives index 0."""
+    _require_cuda(params, energy)
+    if params.dim() != 3 or params.shape[2] != 12 or energy.dim() != 2 or tuple(energy.shape) != tuple(params.shape[:2]):
+        raise ValueError("params must be [K,B,12] and energy [K,B], got %s and %s"
+                         % (tuple(params.shape), tuple(energy.shape)))
+    K, B = int(params.shape[0]), int(params.shape[1])
+    p = params.detach().to(torch.float32).contiguous()
+    e = energy.detach().to(torch.float64).contiguous()
+    out = torch.empty(B, 12, dtype=torch.float32, device=p.device)
+    oe = torch.empty(B, dtype=torch.float64, device=p.device)
+    oi = torch.empty(B, dtype=torch.int32, device=p.device)
+    check(lib().sqr_lsq_select(B, K, ptr(p), ptr(e), ptr(out), ptr(oe), ptr(oi), stream_ptr(p.device)),
+          "sqr_lsq_select")
+    return out, oe, oi
+
+
+def lsq_recover(target, R, iters, e0, lambda0, up, down):
+    """sqr_lsq_recover -> (params [B,12] f32, energy [B] f64, index [B] i32, all_params [3,B,12] f32,
+    all_before [3,B] f64, all_after [3,B] f64, all_accepted [3,B] i32).  One chain of launches on the current
+    stream; no host wait."""
+    t, B, H, W = _image_only(target)
+    dev = t.device
+    out = torch.empty(B, 12, dtype=torch.float32, device=dev)
+    energy = torch.empty(B, dtype=torch.float64, device=dev)
+    index = torch.empty(B, dtype=torch.int32, device=dev)
+    allp = torch.empty(3, B, 12, dtype=torch.float32, device=dev)
+    before = torch.empty(3, B, dtype=torch.float64, device=dev)
+    after = torch.empty(3, B, dtype=torch.float64, device=dev)
+    accepted = torch.empty(3, B, dtype=torch.int32, device=dev)
+    L = lib()
+    wsb = L.sqr_lsq_recover_workspace_bytes(B, int(R))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(L.sqr_lsq_recover(ptr(t), B, H, W, int(R), int(iters), float(e0), float(lambda0), float(up), float(down),
+                            ptr(out), ptr(energy), ptr(index), ptr(allp), ptr(before), ptr(after), ptr(accepted),
+                            ptr(ws), wsb, stream_ptr(dev)), "sqr_lsq_recover")
+    return out, energy, index, allp, before, after, accepted
+
+
 def implicit_render(params, R, tau=1.0, sharpness=100.0):
     """depth_projection (classes.py:232-282) -> [B,R,R] float32 images (no autograd)."""
     _require_cuda(params)

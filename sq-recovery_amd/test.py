@@ -11,6 +11,11 @@ image's own points (sqr.fit.refine, on the GPU) and prints the energy before and
 parameters in the same format.  The energy goes down; the IoU against a label need not go up.
 --refine-method lm runs N Levenberg-Marquardt iterations instead (sqr.fit.refine_lm): the energy is that
 of the projected prediction (a, e, t clamped, q normalised) and the result is a unit quaternion.
+
+--classical builds no network and reads no checkpoint: the parameters are recovered from the image's points
+alone (sqr.fit.recover: Solina & Bajcsy's start from the points' moments, --classical-iters
+Levenberg-Marquardt iterations from each of three axis orders, the lowest energy wins) and printed in the
+same format with that energy and the winning start.  It composes with --refine.
 """
 import argparse
 import os
@@ -44,17 +49,30 @@ def main(argv=None):
     ap.add_argument("--refine-lr", type=float, default=2e-3)
     ap.add_argument("--refine-method", choices=("adam", "lm"), default="adam",
                     help="adam: N Adam steps; lm: N Levenberg-Marquardt iterations (sqr.fit.refine_lm)")
+    ap.add_argument("--classical", action="store_true",
+                    help="no network, no checkpoint: recover the parameters from the image's points alone "
+                         "(sqr.fit.recover, CUDA)")
+    ap.add_argument("--classical-iters", type=int, default=30, metavar="N",
+                    help="Levenberg-Marquardt iterations per start of --classical")
     args = ap.parse_args(argv)
 
-    net = ResNetSQ(outputs=4, pretrained=False).to(args.device)
-    if os.path.exists(args.model):
-        _, net, _, _ = load_model(args.model, net, None)
-    else:
-        print("checkpoint %s not found: using random weights" % args.model)
-    net.eval()
     img = read_image_gray(args.image)
-    a, e, t, q = predict(net, img, args.device)
-    print("Predicted parameters: ")
+    if args.classical:
+        from sqr.fit import recover
+        x = torch.from_numpy(img.astype(np.float32)[None, None] / 255).to(args.device)
+        pred, energy, start = recover(x, iters=args.classical_iters)
+        a, e, t, q = (o.cpu().numpy() for o in torch.split(pred, (3, 2, 3, 4), dim=1))
+        print("Recovered parameters (classical, %d Levenberg-Marquardt iterations per start, LeastSquares energy "
+              "%.6g, start %d): " % (args.classical_iters, energy.item(), start.item()))
+    else:
+        net = ResNetSQ(outputs=4, pretrained=False).to(args.device)
+        if os.path.exists(args.model):
+            _, net, _, _ = load_model(args.model, net, None)
+        else:
+            print("checkpoint %s not found: using random weights" % args.model)
+        net.eval()
+        a, e, t, q = predict(net, img, args.device)
+        print("Predicted parameters: ")
     print("Size a:", a * 255)
     print("Shape e:", e)
     print("Position t:", t * 255)

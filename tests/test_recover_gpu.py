@@ -1,0 +1,545 @@
+"""The classical recovery on the GPU: the starts (sqr_lsq_starts, sqr.losses.lsq_starts), the selection
+(sqr_lsq_select), the whole chain (sqr_lsq_recover, sqr.fit.recover), test.py --classical and
+eval_random.py --method classical (test_random.py's own program with the recovery in place of the network).
+
+The host rules are tests/_recover_ref.py; the float64 and float32 host pipelines on the ten example images are
+the fixture tests/golden/recover.npz (tests/golden/gen_golden_recover.py), so no test here runs a host loop.
+
+Tolerances.  Moments: products of two floats are exact in float64 and a sum has at most R^2 = 1024 terms, so
+each sum is within 1024 x 2^-53 = 1.1e-13 < 1e-12 of the sum of its terms' absolute values; the count is
+exact.  Frame: Jacobi in float64, V^T V = I and det V = 1 to 1e-14, off-diagonals of V^T C V and the
+eigenvalues to 1e-12 x trace C (C: the two-pass float64 covariance of the float32 points).  Starts: a and t
+are float32 roundings of float64 values recomputed here from the returned frame: one float32 ulp; q through
+mat_from_quaternion's quadratic form: 2e-6.  recover: the yardstick of tests/test_lm_refine_gpu.py, per image
+the winning energy over the float64 host pipeline's, at least 1, within twice the worst such ratio of the
+float32 host pipeline; at least five of the ten winners reach IoU 0.9 against their labels (the float64
+pipeline: six, the lowest of them 0.937).  Measured on MI355X: see DESIGN.md, "Recovery without the network".
+"""
+import importlib.util
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import _lm_ref
+import _recover_ref as rr
+from _golden import load
+from _lsq_cases import build_images, example
+from quaternion import mat_from_quaternion_np
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+# (R, H, W): the shape table of tests/test_lm_refine_gpu.py; B = 1, 2, 3 each
+SHAPES = [
+    (8, 16, 16),    # a partly filled block
+    (16, 32, 32),   # exactly one block of 256
+    (32, 32, 32),   # four blocks per sample: the partial sums
+    (12, 32, 32),   # inexact c / R, non-integer resize ratio
+    (16, 24, 40),   # non-square target
+]
+
+
+def _resample(ex, idx, H, W):
+    """Example images idx at HxW (nearest source pixel)."""
+    rows, cols = np.arange(H) * 256 // H, np.arange(W) * 256 // W
+    return np.ascontiguousarray(ex[np.asarray(idx)][:, :, rows][:, :, :, cols])
+
+
+def _nan_holes(ex):
+    x = ex[[9, 0, 1]].copy()
+    x[:, :, 96:160, 64:128] = np.nan
+    return x
+
+
+def _cases():
+    ex, _ = example()
+    out = []
+    for R, H, W in SHAPES:
+        for B in (1, 2, 3):
+            idx = (np.arange(B) + R + B) % 10
+            out.append(dict(name="R%d_%dx%d_B%d" % (R, H, W, B), R=R, true=_resample(ex, idx, H, W)))
+    for kind in ("zero", "onepix", "raw255"):
+        out.append(dict(name=kind + "_R32", R=32, true=build_images(kind, [3, 4, 5], ex)))
+    out.append(dict(name="nanholes_R32", R=32, true=_nan_holes(ex)))
+    return out
+
+
+def _starts_raw(true, R, e0=1.0):
+    """sqr_lsq_starts through the C ABI -> dict of numpy outputs, and the moments [B,10] summed on the host from
+    the workspace's per-block partials in block order."""
+    from sqr._lib import lib, ptr, stream_ptr
+    L = lib()
+    t = torch.tensor(true[:, 0], device=DEV).contiguous()
+    B, H, W = t.shape
+    nblk = (R * R + 255) // 256
+    wsb = L.sqr_lsq_starts_workspace_bytes(B, R)
+    assert wsb == B * nblk * 16 * 8
+    ws = torch.zeros(wsb // 8, dtype=torch.float64, device=DEV)
+    o = dict(starts=torch.empty(3, B, 12, dtype=torch.float32, device=DEV),
+             count=torch.empty(B, dtype=torch.int32, device=DEV),
+             centroid=torch.empty(B, 3, dtype=torch.float64, device=DEV),
+             eigenvalues=torch.empty(B, 3, dtype=torch.float64, device=DEV),
+             frame=torch.empty(B, 3, 3, dtype=torch.float64, device=DEV))
+    rc = L.sqr_lsq_starts(ptr(t), B, H, W, R, e0, ptr(o["starts"]), ptr(o["count"]), ptr(o["centroid"]),
+                          ptr(o["eigenvalues"]), ptr(o["frame"]), ptr(ws), wsb, stream_ptr(DEV))
+    torch.cuda.synchronize()
+    assert rc == 0, L.sqr_last_error_string()
+    out = {k: v.cpu().numpy() for k, v in o.items()}
+    part = ws[:B * nblk * 10].cpu().numpy().reshape(B, nblk, 10)
+    mom = np.zeros((B, 10))
+    for k in range(nblk):
+        mom += part[:, k]
+    out["moments"] = mom
+    return out
+
+
+@pytest.fixture(scope="module")
+def rows():
+    """Per case: the kernel's outputs and the float32 points of every image [3,N] as float64.  Computed once."""
+    out = []
+    for c in _cases():
+        pts = [p.numpy().astype(np.float64) for p in _lm_ref.points_of(c["true"], c["R"], torch.float32)]
+        out.append(dict(name=c["name"], R=c["R"], true=c["true"], pts=pts, ker=_starts_raw(c["true"], c["R"])))
+    return out
+
+
+def _many_points(r):
+    return not r["name"].startswith(("zero", "onepix"))
+
+
+def test_starts_python_wrapper_is_the_c_call(rows):
+    from sqr import losses
+    r = rows[8]
+    starts, info = losses.lsq_starts(torch.tensor(r["true"], device=DEV), r["R"])
+    torch.cuda.synchronize()
+    assert starts.dtype == torch.float32 and info["count"].dtype == torch.int32 and info["frame"].dtype == torch.float64
+    assert np.array_equal(starts.cpu().numpy(), r["ker"]["starts"])
+    for k in ("count", "centroid", "eigenvalues", "frame"):
+        assert np.array_equal(info[k].cpu().numpy(), r["ker"][k]), k
+    with pytest.raises(ValueError):
+        losses.lsq_starts(torch.tensor(r["true"]), r["R"])  # a CPU tensor
+    with pytest.raises(RuntimeError):
+        losses.lsq_starts(torch.tensor(r["true"], device=DEV), r["R"], e0=0.05)
+
+
+def test_moments_vs_float64_sums(rows):
+    worst = 0.0
+    for r in rows:
+        for b, P in enumerate(r["pts"]):
+            x, y, z = P
+            one = np.ones_like(x)
+            terms = [x * x, x * y, x * z, x, y * y, y * z, y, z * z, z, one]
+            got = r["ker"]["moments"][b]
+            assert r["ker"]["count"][b] == P.shape[1] and got[9] == P.shape[1], (r["name"], b)
+            for i, t in enumerate(terms):
+                scale = np.abs(t).sum()
+                err = abs(got[i] - t.sum())
+                assert err <= 1e-12 * scale, (r["name"], b, i, err, scale)
+                worst = max(worst, err / scale if scale else 0.0)
+            if P.shape[1]:
+                np.testing.assert_allclose(r["ker"]["centroid"][b], P.mean(1), rtol=1e-13)
+    print("moments: worst error over the sum of the absolute terms %.2e (bound 1e-12)" % worst)
+
+
+def test_frame_is_a_proper_rotation_that_diagonalises_the_covariance(rows):
+    worst = [0.0, 0.0, 0.0]
+    for r in rows:
+        for b, P in enumerate(r["pts"]):
+            V, lam = r["ker"]["frame"][b], r["ker"]["eigenvalues"][b]
+            orth = np.abs(V.T @ V - np.eye(3)).max()
+            assert orth <= 1e-14 and abs(np.linalg.det(V) - 1) <= 1e-14, (r["name"], b)
+            assert (np.diff(lam) >= 0).all(), (r["name"], b, lam)
+            worst[0] = max(worst[0], orth)
+            if not _many_points(r):
+                continue
+            C = np.cov(P, bias=True)
+            tr = np.trace(C)
+            D = V.T @ C @ V
+            off = np.abs(D - np.diag(np.diagonal(D))).max()
+            ev = np.abs(lam - np.linalg.eigvalsh(C)).max()
+            assert off <= 1e-12 * tr and ev <= 1e-12 * tr, (r["name"], b, off, ev, tr)
+            worst[1], worst[2] = max(worst[1], off / tr), max(worst[2], ev / tr)
+    print("frame: worst |V^T V - I| %.2e (1e-14), off-diagonal / trace %.2e, eigenvalue / trace %.2e (1e-12)"
+          % tuple(worst))
+
+
+def _ulp32(x):
+    return np.spacing(np.abs(np.asarray(x, np.float32)).astype(np.float32)).astype(np.float64)
+
+
+def test_starts_follow_the_returned_frame(rows):
+    worst_q = 0.0
+    for r in rows:
+        if r["name"].startswith("zero"):
+            continue
+        S = r["ker"]["starts"]
+        for b, P in enumerate(r["pts"]):
+            V = r["ker"]["frame"][b]
+            proj = V.T @ P
+            lo, hi = proj.min(1), proj.max(1)
+            half, mid = 0.5 * (hi - lo), 0.5 * (hi + lo)
+            for k in range(3):
+                s = S[k, b]
+                ax = [(k + j) % 3 for j in range(3)]
+                a = np.clip(half[ax].astype(np.float32), np.float32(0.05), np.float32(1))
+                t = np.clip((V[:, ax] @ mid[ax]).astype(np.float32), np.float32(0), np.float32(1))
+                assert (np.abs(s[0:3].astype(np.float64) - a) <= _ulp32(a)).all(), (r["name"], b, k, s[0:3], a)
+                assert (np.abs(s[5:8].astype(np.float64) - t) <= _ulp32(t)).all(), (r["name"], b, k, s[5:8], t)
+                assert (s[3:5] == np.float32(1.0)).all()
+                assert abs(np.linalg.norm(s[8:].astype(np.float64)) - 1) <= 1e-6
+                dq = np.abs(mat_from_quaternion_np(s[8:])[0] - V[:, ax]).max()
+                assert dq <= 2e-6, (r["name"], b, k, dq)
+                worst_q = max(worst_q, dq)
+                assert (s[0:3] >= np.float32(0.05)).all() and (s[0:3] <= 1).all()
+                assert (s[5:8] >= 0).all() and (s[5:8] <= 1).all()
+                # one frame per sample: the sizes are those of start 0 in cyclic order, the position is the same
+                assert np.array_equal(s[0:3], S[0, b][ax]), (r["name"], b, k)
+                assert (np.abs(s[5:8].astype(np.float64) - S[0, b, 5:8]) <= _ulp32(S[0, b, 5:8])).all()
+    print("starts: worst |mat_from_quaternion(q) - frame| %.2e (bound 2e-6)" % worst_q)
+
+
+def test_degenerate_images(rows):
+    by = {r["name"]: r for r in rows}
+    for r in rows:
+        assert all(np.isfinite(v).all() for v in r["ker"].values()), r["name"]
+    z = by["zero_R32"]["ker"]
+    assert not z["count"].any() and not z["centroid"].any() and not z["eigenvalues"].any() and not z["moments"].any()
+    assert np.array_equal(z["frame"], np.tile(np.eye(3), (3, 1, 1)))
+    assert np.array_equal(z["starts"], np.tile(rr.default_start(1.0), (3, 3, 1)))
+    o = by["onepix_R32"]
+    assert o["ker"]["count"].tolist() == [1, 1, 1]
+    assert (o["ker"]["starts"][:, :, 0:3] == np.float32(0.05)).all()  # zero extents clamp
+    for b, P in enumerate(o["pts"]):
+        for k in range(3):
+            t = o["ker"]["starts"][k, b, 5:8].astype(np.float64)
+            assert (np.abs(t - P[:, 0]) <= _ulp32(P[:, 0])).all(), (b, k, t, P[:, 0])
+    # an image without points in a batch leaves the others alone; a NaN pixel is a zero pixel
+    n = by["nanholes_R32"]
+    mixed = n["true"].copy()
+    mixed[1] = 0
+    m = _starts_raw(mixed, 32)
+    assert m["count"][1] == 0 and np.array_equal(m["starts"][:, 1], np.tile(rr.default_start(1.0), (3, 1)))
+    for b in (0, 2):
+        for k in ("starts", "count", "centroid", "eigenvalues", "frame", "moments"):
+            x, y = m[k], n["ker"][k]
+            assert np.array_equal(x[:, b] if k == "starts" else x[b], y[:, b] if k == "starts" else y[b]), (b, k)
+    zeros = np.nan_to_num(n["true"], nan=0.0)
+    assert np.isnan(n["true"]).any() and (n["ker"]["count"] > 0).all()
+    hz = _starts_raw(zeros, 32)
+    for k, v in hz.items():
+        assert np.array_equal(v, n["ker"][k]), k
+    # e0 is passed through
+    e = _starts_raw(n["true"], 32, e0=0.5)
+    assert (e["starts"][:, :, 3:5] == np.float32(0.5)).all()
+    assert np.array_equal(np.delete(e["starts"], [3, 4], 2), np.delete(n["ker"]["starts"], [3, 4], 2))
+
+
+def test_starts_samples_independent_and_runs_bitwise_equal(rows):
+    r = [x for x in rows if x["name"] == "R32_32x32_B3"][0]
+    again = _starts_raw(r["true"], r["R"])
+    for k, v in again.items():
+        assert np.array_equal(v, r["ker"][k]), k
+    for i in range(3):
+        one = _starts_raw(r["true"][i:i + 1], r["R"])
+        for k, v in one.items():
+            want = r["ker"][k][:, i] if k == "starts" else r["ker"][k][i]
+            assert np.array_equal(v[:, 0] if k == "starts" else v[0], want), (i, k)
+
+
+def test_select_against_the_host_rule():
+    from sqr import losses
+    nan = np.nan
+    e3 = np.array([[3.0, 1.0, 1.0, nan, nan, 2.0, nan, np.inf, -0.0],
+                   [2.0, 1.0, 0.5, 4.0, nan, nan, nan, -np.inf, 0.0],
+                   [1.0, 2.0, 0.5, 3.0, nan, 2.0, 0.0, 0.0, 0.0]])
+    rng = np.random.default_rng(5)
+    for e in (e3, e3[:1], e3[1:]):
+        K, B = e.shape
+        p = rng.random((K, B, 12)).astype(np.float32)
+        out, oe, oi = losses.lsq_select(torch.tensor(p, device=DEV), torch.tensor(e, device=DEV))
+        torch.cuda.synchronize()
+        assert out.dtype == torch.float32 and oe.dtype == torch.float64 and oi.dtype == torch.int32
+        idx = rr.select(e)
+        assert np.array_equal(oi.cpu().numpy(), idx), (oi, idx)
+        assert np.array_equal(out.cpu().numpy(), p[idx, np.arange(B)])
+        got, want = oe.cpu().numpy(), e[idx, np.arange(B)]
+        assert np.array_equal(got.view(np.int64), want.view(np.int64))  # bitwise, NaN and -0.0 included
+    assert e3.shape[1] == 9 and rr.select(e3).tolist() == [2, 0, 1, 2, 0, 0, 2, 1, 0]
+
+
+# ------------------------------------------------------------------------------------------ the whole chain
+@pytest.fixture(scope="module")
+def run():
+    """sqr.fit.recover on the ten example images at 256x256, R = 32, 30 iterations.  Computed once."""
+    from sqr import fit
+    ex, labels = example()
+    img = torch.tensor(ex, device=DEV)
+    params, energy, index, info = fit.recover(img, iters=30, render_size=32, return_info=True)
+    torch.cuda.synchronize()
+    assert torch.equal(img, torch.tensor(ex, device=DEV))  # the input is left alone
+    assert params.dtype == torch.float32 and params.shape == (10, 12) and not params.requires_grad
+    assert energy.dtype == torch.float64 and energy.shape == (10,)
+    assert index.dtype == torch.int32 and index.shape == (10,)
+    assert info["params"].shape == (3, 10, 12) and info["starts"].shape == (3, 10, 12)
+    for k in ("energy_before", "energy_after", "accepted"):
+        assert info[k].shape == (3, 10), k
+    assert info["count"].shape == (10,) and info["frame"].shape == (10, 3, 3)
+    return dict(img=img, labels=labels, params=params, energy=energy, index=index, info=info, fix=load("recover.npz"))
+
+
+def test_recover_descends_selects_the_minimum_and_returns_valid_parameters(run):
+    from sqr import losses
+    info = run["info"]
+    before, after = info["energy_before"].cpu().numpy(), info["energy_after"].cpu().numpy()
+    acc, idx = info["accepted"].cpu().numpy(), run["index"].cpu().numpy()
+    for i in range(10):
+        print("image %d: before %s after %s accepted %s start %d" % (
+            i, " ".join("%.4g" % v for v in before[:, i]), " ".join("%.4g" % v for v in after[:, i]),
+            acc[:, i].tolist(), idx[i]))
+    assert np.isfinite(before).all() and np.isfinite(after).all()
+    assert (after <= before).all()  # exact: the same kernel
+    assert (acc >= 0).all() and (acc <= 30).all()
+    energy = run["energy"].cpu().numpy()
+    assert np.array_equal(energy, after.min(0)) and np.array_equal(idx, rr.select(after))
+    assert np.array_equal(energy, after[idx, np.arange(10)])
+    out = run["params"].cpu().numpy()
+    assert np.array_equal(out, info["params"].cpu().numpy()[idx, np.arange(10)])
+    _, _, e = losses.least_squares_normal_eq(run["img"], run["params"], 32)
+    assert torch.equal(e, run["energy"])  # bitwise the normal-equations kernel's energy at the result
+    assert np.isfinite(out).all()
+    assert (out[:, 0:3] >= np.float32(0.05)).all() and (out[:, 0:3] <= 1).all()
+    assert (out[:, 3:5] >= np.float32(0.1)).all() and (out[:, 3:5] <= 1).all()
+    assert (out[:, 5:8] >= 0).all() and (out[:, 5:8] <= 1).all()
+    assert np.abs(np.linalg.norm(out[:, 8:].astype(np.float64), axis=1) - 1).max() <= 1e-6
+    # the starts the chain refined are sqr_lsq_starts' (the fixture's float64 host starts to a float32 ulp or two)
+    starts = info["starts"].cpu().numpy()
+    np.testing.assert_allclose(np.swapaxes(starts, 0, 1), run["fix"]["starts_64"], rtol=0, atol=2e-6)
+
+
+def test_recover_winning_energy_vs_float64_pipeline(run):
+    """Accept decisions differ between precisions, so no trajectory and no single start is compared: per image
+    the winning energy over the float64 host pipeline's (fixture), at least 1, within twice the worst such
+    ratio of the float32 host pipeline (fixture)."""
+    fix = run["fix"]
+    after = run["info"]["energy_after"].cpu().numpy()
+    a64, a32 = fix["after_64"], fix["after_32"]
+    for i in range(10):
+        print("image %d per-start kernel / float64: %s | float32 host / float64: %s" % (
+            i, " ".join("%.4f" % (after[k, i] / a64[i, k]) for k in range(3)),
+            " ".join("%.4f" % (a32[i, k] / a64[i, k]) for k in range(3))))
+    w64, w32 = a64[np.arange(10), fix["winner_64"]], a32[np.arange(10), fix["winner_32"]]
+    win = run["energy"].cpu().numpy()
+    rk, r32 = np.maximum(win / w64, 1), np.maximum(w32 / w64, 1)
+    for i in range(10):
+        print("image %d winner: float64 %.6g (start %d) | float32 host %.6g (%.4f) | kernel %.6g (start %d, %.4f)"
+              % (i, w64[i], fix["winner_64"][i], w32[i], w32[i] / w64[i], win[i], run["index"][i].item(),
+                 win[i] / w64[i]))
+    print("worst winner ratio: float32 host %.4f kernel %.4f" % (r32.max(), rk.max()))
+    assert (rk <= 2 * r32.max()).all(), (rk, r32.max())
+
+
+def test_recover_iou_floor(run):
+    """At least five of the ten winners reach IoU 0.9 (grid 64) against their labels: a floor against a broken
+    start rule, not a promise (the float64 host pipeline has six, the lowest of them 0.937)."""
+    import classes
+    iou = classes.IoUAccuracy(64, DEV, reduce=False)(torch.tensor(run["labels"], device=DEV), run["params"]).cpu().numpy()
+    for i in range(10):
+        print("image %d: IoU %.3f (float64 host pipeline %.3f)" % (i, iou[i], run["fix"]["iou_winner_64"][i]))
+    print("winners with IoU >= 0.9: %d of 10 (float64 host pipeline %d)"
+          % ((iou >= 0.9).sum(), (run["fix"]["iou_winner_64"] >= 0.9).sum()))
+    assert (iou >= 0.9).sum() >= 5, iou
+
+
+def test_recover_batch_independence_repeatability_and_empty_image(run):
+    from sqr import fit
+    again = fit.recover(run["img"], iters=30, render_size=32)
+    for x, k in zip(again, ("params", "energy", "index")):
+        assert torch.equal(x, run[k]), k
+    img = run["img"][[2, 7, 4]].clone()
+    img[1] = 0
+    p, e, i = fit.recover(img, iters=30, render_size=32)
+    assert torch.equal(p[0], run["params"][2]) and torch.equal(p[2], run["params"][4])
+    assert e[0] == run["energy"][2] and e[2] == run["energy"][4] and i[0] == run["index"][2] and i[2] == run["index"][4]
+    assert e[1].item() == 0.0 and i[1].item() == 0
+    assert np.array_equal(p[1].cpu().numpy(), rr.default_start(1.0))
+
+
+def test_recover_captured_in_a_graph_replays_bitwise(run):
+    from sqr import fit
+    img = run["img"].clone()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        res = fit.recover(img, iters=30, render_size=32)
+    other = run["img"].flip(0).contiguous()
+    eager_other = fit.recover(other, iters=30, render_size=32)
+    for src, want in ((run["img"], [run[k] for k in ("params", "energy", "index")]), (other, eager_other)):
+        img.copy_(src)
+        g.replay()
+        torch.cuda.synchronize()
+        assert all(torch.equal(x, y) for x, y in zip(res, want))
+
+
+GUARD = 64
+
+
+def _guarded(n, dtype, fill):
+    buf = torch.full((n + 2 * GUARD,), fill, dtype=dtype, device=DEV)
+    return buf, buf[GUARD:GUARD + n]
+
+
+def _intact(buf, n, fill):
+    return bool((buf[:GUARD] == fill).all()) and bool((buf[GUARD + n:] == fill).all())
+
+
+@pytest.mark.parametrize("R,H,W,B", [(8, 16, 16, 3), (32, 32, 32, 2), (12, 24, 40, 3)])
+def test_c_abi_writes_inside_its_buffers_only(R, H, W, B):
+    """Guard words around every output and the workspace of sqr_lsq_starts and sqr_lsq_recover, each given exactly
+    the bytes its _workspace_bytes asks for; a workspace one byte short is an error and launches nothing."""
+    from sqr._lib import lib, ptr, stream_ptr
+    L = lib()
+    ex, _ = example()
+    t = torch.tensor(_resample(ex, np.arange(B) % 10, H, W)[:, 0], device=DEV).contiguous()
+    nblk = (R * R + 255) // 256
+    wsb = L.sqr_lsq_starts_workspace_bytes(B, R)
+    assert wsb == B * nblk * 16 * 8
+    f = -7.25
+    bufs = dict(starts=_guarded(3 * B * 12, torch.float32, f), count=_guarded(B, torch.int32, -7),
+                centroid=_guarded(3 * B, torch.float64, f), eig=_guarded(3 * B, torch.float64, f),
+                frame=_guarded(9 * B, torch.float64, f), ws=_guarded(wsb, torch.uint8, 0xA5))
+    fills = dict(starts=f, count=-7, centroid=f, eig=f, frame=f, ws=0xA5)
+
+    def call(nbytes):
+        rc = L.sqr_lsq_starts(ptr(t), B, H, W, R, 1.0, *[ptr(bufs[k][1]) for k in ("starts", "count", "centroid", "eig",
+                                                                                  "frame", "ws")], nbytes, stream_ptr(DEV))
+        torch.cuda.synchronize()
+        return rc
+
+    assert call(wsb - 1) == -1 and b"workspace" in L.sqr_last_error_string()
+    assert all(bool((b[0] == fills[k]).all()) for k, b in bufs.items())  # nothing was launched
+    assert call(wsb) == 0, L.sqr_last_error_string()
+    for k, (buf, view) in bufs.items():
+        assert _intact(buf, view.numel(), fills[k]), k
+        if k != "ws":
+            assert bool((view != fills[k]).all()) and (k == "count" or bool(torch.isfinite(view).all())), k
+    # the whole chain
+    wsb = L.sqr_lsq_recover_workspace_bytes(B, R)
+    assert wsb == B * 15 * 8 + max(B * nblk * 16 * 8, L.sqr_lsq_lm_refine_workspace_bytes(B, R)) + B * 36 * 4 + B * 4
+    bufs = dict(out=_guarded(B * 12, torch.float32, f), energy=_guarded(B, torch.float64, f),
+                index=_guarded(B, torch.int32, -7), allp=_guarded(3 * B * 12, torch.float32, f),
+                before=_guarded(3 * B, torch.float64, f), after=_guarded(3 * B, torch.float64, f),
+                acc=_guarded(3 * B, torch.int32, -7), ws=_guarded(wsb, torch.uint8, 0xA5))
+    fills = dict(out=f, energy=f, index=-7, allp=f, before=f, after=f, acc=-7, ws=0xA5)
+
+    def recover(nbytes, e0=1.0):
+        rc = L.sqr_lsq_recover(ptr(t), B, H, W, R, 3, e0, 1e-3, 10.0, 0.1,
+                               *[ptr(bufs[k][1]) for k in ("out", "energy", "index", "allp", "before", "after", "acc",
+                                                           "ws")], nbytes, stream_ptr(DEV))
+        torch.cuda.synchronize()
+        return rc
+
+    assert recover(wsb - 1) == -1 and b"workspace" in L.sqr_last_error_string()
+    assert recover(wsb, e0=0.05) == -1 and b"e0" in L.sqr_last_error_string()
+    assert recover(wsb, e0=1.5) == -1
+    assert all(bool((b[0] == fills[k]).all()) for k, b in bufs.items())  # nothing was launched
+    assert recover(wsb) == 0, L.sqr_last_error_string()
+    for k, (buf, view) in bufs.items():
+        assert _intact(buf, view.numel(), fills[k]), k
+        if k != "ws":
+            assert bool((view != fills[k]).all()), k
+    after, before = bufs["after"][1].view(3, B), bufs["before"][1].view(3, B)
+    assert bool((after <= before).all()) and bool(torch.equal(bufs["energy"][1], after.min(0).values))
+    assert bool((bufs["acc"][1] >= 0).all()) and bool((bufs["acc"][1] <= 3).all())
+    assert bool((bufs["index"][1] >= 0).all()) and bool((bufs["index"][1] <= 2).all())
+
+
+# ------------------------------------------------------------------------------------------ the command lines
+def _load_script(name):
+    from conftest import PKG
+    spec = importlib.util.spec_from_file_location("sq_%s_recover" % name, os.path.join(PKG, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _write_bmp(path, img):
+    """A bottom-up 24-bit BMP, as the scanner writes (tests/test_lm_refine_gpu.py builds the same)."""
+    h, w = img.shape
+    stride = (w * 3 + 3) & ~3
+    data = np.zeros((h, stride), np.uint8)
+    data[:, :w * 3] = np.repeat(img[::-1], 3, axis=1)
+    hdr = b"BM" + (54 + data.size).to_bytes(4, "little") + b"\0\0\0\0" + (54).to_bytes(4, "little")
+    dib = (40).to_bytes(4, "little") + w.to_bytes(4, "little") + h.to_bytes(4, "little") + \
+        (1).to_bytes(2, "little") + (24).to_bytes(2, "little") + b"\0" * 24
+    path.write_bytes(hdr + dib + data.tobytes())
+
+
+def test_test_py_classical(tmp_path, capsys, run):
+    bmp = tmp_path / "x.bmp"
+    _write_bmp(bmp, load("example_images.npz")["images"][4])
+    mod = _load_script("test")
+    a, e, t, q = mod.main(["--image", str(bmp), "--model", str(tmp_path / "none.pt"), "--device", DEV, "--classical"])
+    out = capsys.readouterr().out
+    assert "not found" not in out and "Predicted parameters" not in out  # no network, no checkpoint
+    m = re.search(r"Recovered parameters \(classical, 30 Levenberg-Marquardt iterations per start, LeastSquares "
+                  r"energy (\S+), start (\d)\):", out)
+    assert m, out
+    assert out.count("Size a:") == 1 and out.count("Rotation q:") == 1
+    assert a.shape == (1, 3) and e.shape == (1, 2) and t.shape == (1, 3) and q.shape == (1, 4)
+    assert all(np.isfinite(v).all() for v in (a, e, t, q))
+    # the same image as in the batch of ten: the same result
+    assert np.array_equal(np.concatenate([a, e, t, q], 1)[0], run["params"][4].cpu().numpy())
+    assert float(m.group(1)) == pytest.approx(run["energy"][4].item(), rel=1e-5) and int(m.group(2)) == run["index"][4].item()
+    # it composes with --refine
+    a2, _, _, q2 = mod.main(["--image", str(bmp), "--device", DEV, "--classical", "--classical-iters", "5",
+                             "--refine", "3", "--refine-method", "lm"])
+    out = capsys.readouterr().out
+    assert "classical, 5 Levenberg-Marquardt" in out and out.count("Size a:") == 2
+    m = re.search(r"Refined parameters \(3 Levenberg-Marquardt iterations, LeastSquares energy (\S+) -> (\S+)\):", out)
+    assert m and float(m.group(2)) <= float(m.group(1))
+    assert a2.shape == (1, 3) and abs(np.linalg.norm(q2.astype(np.float64)) - 1) <= 1e-6
+
+
+def test_eval_random_method_classical(tmp_path, capsys):
+    """eval_random.py --method classical --n 8 --batch 4 --render-size 32: test_random.py's own program with
+    sqr.fit.recover in place of the net; no network, no checkpoint."""
+    import classes
+    from sqr import fit, losses
+    mod = _load_script("eval_random")
+    res = tmp_path / "results.txt"
+    ious = mod.main(["--method", "classical", "--n", "8", "--batch", "4", "--render-size", "32", "--results", str(res),
+                     "--model", str(tmp_path / "none.pt"), "--device", DEV])
+    out = capsys.readouterr().out
+    assert "not found" not in out and "random weights" not in out and "Mean:" in out and "Std:" in out
+    assert ious.shape == (8,) and np.isfinite(ious).all() and (ious >= 0).all() and (ious <= 1).all()
+    text = res.read_text()
+    assert text.count("---------- Example") == 8 and text.count("Pred params:") == 8 and text.count("- Accuracy:") == 8
+    # test_random.py's instances, and the recovery's parameters of their renders: nothing else predicted them
+    labels = classes.sample_sq_params(np.random.default_rng(0), 8)
+    true = torch.tensor(labels, device=DEV)
+    fmt = mod.test_random._fmt
+    for i in (0, 4):
+        x = losses.scan_render(true[i:i + 4], 256, 255).unsqueeze(1)
+        pred = fit.recover(x)[0].cpu().numpy()
+        for k in range(4):
+            assert "True params: " + fmt(labels[i + k]) in text and "Pred params: " + fmt(pred[k]) in text, i + k
+    # the hooks are put back
+    import models
+    assert mod.test_random.ResNetSQ is models.ResNetSQ
+    print("eval_random classical IoUs:", " ".join("%.3f" % v for v in ious))
+
+
+def test_eval_random_default_is_test_random(tmp_path, capsys):
+    """Without --method (or with network) eval_random.py is test_random.py: the same output and IoUs."""
+    mod = _load_script("eval_random")
+    args = ["--n", "4", "--batch", "4", "--render-size", "16", "--model", str(tmp_path / "none.pt"), "--device", DEV]
+    outs = []
+    for name, main, extra in (("a", mod.test_random.main, []), ("b", mod.main, []), ("c", mod.main, ["--method", "network"])):
+        torch.manual_seed(0)
+        ious = main(extra + args + ["--results", str(tmp_path / name)])
+        outs.append((ious, capsys.readouterr().out, (tmp_path / name).read_text()))
+    assert "random weights" in outs[0][1]
+    for o in outs[1:]:
+        assert np.array_equal(o[0], outs[0][0]) and o[1] == outs[0][1] and o[2] == outs[0][2]

@@ -14,6 +14,12 @@ times the Levenberg-Marquardt refinement at the same shapes: one normal-equation
 sqr.fit.refine_lm, each eagerly and inside a replayed graph, next to the least_squares forward + backward
 call and to sqr.fit.refine's 200 Adam steps in the same process.
 
+    python tools/loss_time.py recover
+
+times the classical recovery (sqr.fit.recover, 30 iterations per start) at the same shapes, eagerly and inside
+a replayed graph, next to its starts alone and to one sqr.fit.refine_lm with the same iterations in the same
+process, and reports the energies, the winning starts and the IoU against the labels of that batch.
+
     python tools/loss_time.py scan
 
 times the scanner-style depth render (sqr_scan_render) at B = 256, S = 256, eagerly and inside a replayed
@@ -120,6 +126,33 @@ def lm(dev, R=64, H=256, B=64):
     return res
 
 
+def recover(dev, R=64, H=256, B=64, iters=30):
+    """sqr.fit.recover (the starts, three refinements, the selection) eagerly and inside a graph, next to the
+    starts alone and to one refine_lm with the same `iters` from labels + N(0, 0.02), at the shapes of the lm
+    mode, on scanner-style images of random labels."""
+    from sqr import fit
+    p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
+    img = losses.scan_render(p, H, 255).unsqueeze(1).contiguous()
+    torch.manual_seed(0)
+    pred = (p + 0.02 * torch.randn_like(p)).contiguous()
+    res = {"shape": "R%d_H%d_B%d" % (R, H, B), "iters": iters,
+           "points_per_image": round(float((torch.nn.functional.interpolate(img, size=(R, R)) > 0).sum()) / B, 1),
+           "starts_eager_ms": round(_eager_ms(lambda: losses.lsq_starts(img, R)), 4),
+           "starts_in_graph_us": round(_graph_us(lambda: losses.lsq_starts(img, R)), 2),
+           "refine_lm_eager_ms": round(_eager_ms(lambda: fit.refine_lm(img, pred, iters=iters, render_size=R)), 4),
+           "refine_lm_in_graph_us": round(_graph_us(lambda: fit.refine_lm(img, pred, iters=iters, render_size=R)), 2),
+           "recover_eager_ms": round(_eager_ms(lambda: fit.recover(img, iters=iters, render_size=R)), 4),
+           "recover_in_graph_us": round(_graph_us(lambda: fit.recover(img, iters=iters, render_size=R)), 2)}
+    res["recover_over_refine_lm_in_graph"] = round(res["recover_in_graph_us"] / res["refine_lm_in_graph_us"], 3)
+    out, energy, index, info = fit.recover(img, iters=iters, render_size=R, return_info=True)
+    iou = classes.IoUAccuracy(64, dev, reduce=False)(p, out)
+    res["energy_mean"] = {"starts": info["energy_before"][0].mean().item(), "recovered": energy.mean().item()}
+    res["winning_start_counts"] = torch.bincount(index.long(), minlength=3).tolist()
+    res["iou64_mean"] = round(iou.mean().item(), 4)
+    res["iou64_share_above_0.9"] = round((iou >= 0.9).double().mean().item(), 4)
+    return res
+
+
 def scan(dev, S=256, B=256, host_images=16):
     from sqr import cpu
     p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
@@ -148,6 +181,10 @@ def main():
     out = {"env": {k: v for k, v in os.environ.items() if k.startswith("SQR_")}}
     if sys.argv[1:] == ["scan"]:
         out["scan"] = scan(dev)
+        print(json.dumps(out))
+        return
+    if sys.argv[1:] == ["recover"]:
+        out["recover"] = recover(dev)
         print(json.dumps(out))
         return
     if sys.argv[1:] == ["lm"]:
