@@ -27,6 +27,9 @@
  *   sqr_lsq_starts, sqr_lsq_select, sqr_lsq_recover
  *                              no counterpart: that method's start from the image's points alone (centre of
  *                              gravity, principal axes, extents) and the best of three refined starts
+ *   sqr_lsq_starts6, sqr_lsq_lm_refine_multi, sqr_lsq_free_space, sqr_lsq_recover_multi
+ *                              no counterpart: three more, depth-aware starts, all starts refined as one batch,
+ *                              and the winner chosen by point energy plus a free-space energy over every ray
  *   sqr_iou_counts             torch/classes.py:374-447  IoUAccuracy (ins_outs :394-426, __call__ :428-447)
  *   sqr_conv2d_fwd / _bwd_data / _bwd_weight
  *                              torch.nn.Conv2d as used by torchvision resnet18 inside ResNetSQ
@@ -254,6 +257,69 @@ int sqr_lsq_recover(const float* target, int B, int H, int W, int R, int iters, 
                     double down, float* params_out, double* energy_out, int* index_out, float* all_params,
                     double* all_before, double* all_after, int* all_accepted, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* sqr_lsq_lm_refine over K x B samples in one chain: params_in [K,B,12], sample k B + b on image b of target
+ * [B,H,W].  Every sample is on its own and every sum has a fixed order, so the outputs (params_out [K,B,12],
+ * energy_before / energy_after [K,B] f64, accepted [K,B] i32) are bitwise what K calls of sqr_lsq_lm_refine
+ * on the K slices return.  Workspace: sqr_lsq_lm_refine_workspace_bytes(K * B, R).  K,B >= 1, K * B <= 65535;
+ * the other arguments and errors as sqr_lsq_lm_refine. */
+int sqr_lsq_lm_refine_multi(const float* params_in, const float* target, int K, int B, int H, int W, int R, int iters,
+                            double lambda0, double up, double down, float* params_out, double* energy_before,
+                            double* energy_after, int* accepted, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* sqr_lsq_starts with three more, depth-aware starts: starts [6,B,12] f32; starts 0..2 are sqr_lsq_starts'
+ * bitwise.  A depth image shows the front half of the body, so along the frame axis nearest the viewing
+ * direction the points' extent is about half the true one.  j = the column of V with the largest |V[2][j]| (the
+ * first on a tie), ext = max_j - min_j of V^T p; V[2][j] > 0: min_j -= depth ext, else max_j += depth ext (the
+ * viewer is at +z, the hidden half at smaller z); then half-extents, midpoint, clamps, the three cyclic axis
+ * orders and the quaternion as for starts 0..2.  depth = 0 repeats starts 0..2 bitwise in 3..5.  Images
+ * without points and values that are not finite fall back as in sqr_lsq_starts.  0 <= depth <= 8; workspace
+ * (sqr_lsq_starts_workspace_bytes), the other outputs, arguments and errors as sqr_lsq_starts. */
+int sqr_lsq_starts6(const float* target, int B, int H, int W, int R, float e0, float depth, float* starts, int* count,
+                    double* centroid, double* eigenvalues, double* frame, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
+/* Workspace (bytes, device) needed by sqr_lsq_free_space for S samples at render size R. */
+size_t sqr_lsq_free_space_workspace_bytes(int S, int R);
+
+/* Free-space energy of S superquadrics against B depth images, sample s on image s mod B (S = K B: a [K,B]
+ * layout): what the image shows to be empty must stay empty.  Pixels and rays are sqr_least_squares_fwd_bwd's:
+ * resized pixel (r, c) is the ray x = c / R, y = 1 - r / R.  Along the segment [zlo, 4] of each ray (4: the scan
+ * render's upper clip), zlo = z + margin for a pixel z > 0 (nothing lies in front of the visible surface) and
+ * zlo = 0 for a pixel <= 0 (the scanner would have seen a surface there); a NaN pixel and an empty segment add
+ * nothing:
+ *   energy_fs [S] f64 = a0 a1 a2 sum_pixels min(F(x, y, z*) - 1, 0)^2,  z* = the minimiser of F on the segment,
+ * F the LeastSquares point term's (clamped a, e, t, q as given, the zero fix).  F^(1/e1) is convex along the
+ * ray, so z* comes from a 26-step bisection on the sign of its derivative, clipped to the segment; a segment
+ * outside the slab |u_i| <= 1 adds an exact zero.  Per-lane terms fp32, every sum float64 in a fixed order:
+ * bitwise reproducible, a sample's value independent of the rest of the batch.  Two launches, no host wait.
+ * 1 <= B, S a multiple of B, S <= 65535, 1 <= R <= 1024, H,W >= 1, margin >= 0; otherwise, or with a short
+ * workspace, SQR_E_INVALID_ARG and nothing is launched. */
+int sqr_lsq_free_space(const float* params, const float* target, int S, int B, int H, int W, int R, float margin,
+                       double* energy_fs, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_lsq_recover_multi for K = nstarts + Kx starts of B images. */
+size_t sqr_lsq_recover_multi_workspace_bytes(int K, int B, int R);
+
+/* The recovery from K = nstarts + Kx starts in one chain: the starts (nstarts = 3: sqr_lsq_starts', 6:
+ * sqr_lsq_starts6's), the caller's `extra` starts [Kx,B,12] behind them (nullable with Kx = 0; a network's
+ * prediction, for instance), one sqr_lsq_lm_refine_multi over the K B samples, one sqr_lsq_free_space of the
+ * K B results, score = energy_after + w_fs energy_fs (w_fs = 0: energy_after itself, bitwise) and
+ * sqr_lsq_select on the score.  No host wait, no allocation: capturable.
+ *   params_out [B,12] f32, energy_out [B] f64, energy_fs_out [B] f64, index_out [B] i32 : the winner, its point
+ *   energy, its free-space energy, its start
+ *   all_starts [K,B,12] f32, all_params [K,B,12] f32, all_before / all_after / all_fs / all_score [K,B] f64,
+ *   all_accepted [K,B] i32 : every start, its refined parameters, point energy at the projected start and at the
+ *   end, free-space energy and score at the end, accepted steps.
+ * With nstarts = 3, Kx = 0 and w_fs = 0 the winner and the per-start outputs are sqr_lsq_recover's bitwise.
+ * K B <= 65535, w_fs >= 0; the other arguments and errors as sqr_lsq_starts6, sqr_lsq_lm_refine and
+ * sqr_lsq_free_space. */
+int sqr_lsq_recover_multi(const float* target, int B, int H, int W, int R, int iters, int nstarts, float e0,
+                          float depth, const float* extra, int Kx, double lambda0, double up, double down, double w_fs,
+                          float margin, float* params_out, double* energy_out, double* energy_fs_out, int* index_out,
+                          float* all_starts, float* all_params, double* all_before, double* all_after, double* all_fs,
+                          double* all_score, int* all_accepted, void* workspace, size_t workspace_bytes, void* stream);
 
 /* IoUAccuracy(R): per-sample voxel counts [B,2] int64 = (|in_true & in_pred|, |in_true | in_pred|),
  * computed in float64 like the reference. */

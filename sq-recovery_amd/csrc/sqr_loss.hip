@@ -1,7 +1,8 @@
 // Fused superquadric losses for gfx950: ImplicitLoss (render + MAE + analytic gradient),
 // ExplicitLoss (occupancy MSE + gradient), LeastSquares (point-set energy + gradient), IoUAccuracy
 // counts, the scanner-style hard depth render (scan_render_kernel) and the classical recovery's starts and
-// selection around the Levenberg-Marquardt loop (lsq_moments_kernel .. lsq_select_kernel).
+// selection around the Levenberg-Marquardt loop (lsq_moments_kernel .. lsq_select_kernel), with the free-space
+// energy over every pixel's ray that the multi-start recovery selects by (free_space_kernel).
 //
 // Reference algorithm (timoblak/sq-recovery, torch/):
 //   grid               classes.py:217-222 (linspace, exact 0 -> 1e-4), :121-126 (arange, R+1 points)
@@ -873,11 +874,12 @@ __device__ __forceinline__ void lsq_point_row(const SQ& s, float dx, float dy, f
   row[13] = row[14] = row[15] = 0.f;
 }
 
-// grid: (blocks_per_sample, B); one thread per resized pixel.  partials: [B][nblk][16][16] float64
+// grid: (blocks_per_sample, S); one thread per resized pixel.  partials: [S][nblk][16][16] float64.  Sample b
+// reads image b mod Bimg (the batched multi-start refinement's [K,Bimg] layout; Bimg = S: one image each)
 template <int NT>
 __global__ void __launch_bounds__(NT) lsq_normal_eq_kernel(const float* __restrict__ params,
-                                                           const float* __restrict__ target, int H, int W, int R,
-                                                           double* __restrict__ partials) {
+                                                           const float* __restrict__ target, int Bimg, int H, int W,
+                                                           int R, double* __restrict__ partials) {
   static_assert(NT == kNeqP, "one thread per entry of the block's Gram matrix");
   typedef double d4 __attribute__((ext_vector_type(4)));
   __shared__ float4 tile[NT / 64][64 * kNeqT / 4];
@@ -896,7 +898,7 @@ __global__ void __launch_bounds__(NT) lsq_normal_eq_kernel(const float* __restri
     const float sh = (float)H / (float)R, sw = (float)W / (float)R;
     const int sr = min((int)floorf((float)r * sh), H - 1);
     const int sc = min((int)floorf((float)c * sw), W - 1);
-    const float z = target[((size_t)b * H + sr) * W + sc];
+    const float z = target[((size_t)(b % Bimg) * H + sr) * W + sc];
     if (z > 0.f) {  // classes.py:363 (false for NaN)
       const float gx = (float)c / (float)R, gy = 1.f - (float)r / (float)R;
       lsq_point_row(s, gx - s.t[0], gy - s.t[1], z - s.t[2], row);
@@ -1297,16 +1299,29 @@ __global__ void __launch_bounds__(NT) lsq_extents_kernel(const float* __restrict
 // t = M_k (midpoint of the extents), clamped into [0, 1]; e = (e0, e0); q = the xyzw quaternion of M_k,
 // taken from the largest of (trace, m00, m11, m22) (the first on a tie), so that the divisor s = 4 |largest
 // component of q| >= 2.  No point, or a value that is not finite: a = 0.05, e = e0, t = 0.5, q = (0,0,0,1).
-__global__ void __launch_bounds__(64) lsq_starts_kernel(int B, int nblk, float e0, const int* __restrict__ count,
+//
+// nsets = 2 (sqr_lsq_starts6): starts [6,B,12], starts 3..5 are the depth-aware ones.  A depth image shows the
+// front half of the body only, so the extent along the frame axis nearest the viewing direction is about half
+// the true one and its midpoint too near the viewer (at +z).  ja = the column of V with the largest |V[2][ja]|
+// (the first on a tie), ext = max - min along it; the hidden side is stretched by depth * ext: V[2][ja] > 0:
+// min -= depth * ext, else max += depth * ext.  Everything after that is the same code with the same operands
+// as starts 0..2, which take the stretch 0 * ext: x - 0 * ext = x exactly, so depth = 0 gives starts 0..2 again.
+__global__ void __launch_bounds__(64) lsq_starts_kernel(int B, int nblk, int nsets, float e0, float depth,
+                                                        const int* __restrict__ count,
                                                         const double* __restrict__ frame,
                                                         const double* __restrict__ extents,
                                                         float* __restrict__ starts) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= 3 * B) return;
-  const int k = idx / B, b = idx - k * B;
+  if (idx >= 3 * nsets * B) return;
+  const int kall = idx / B, b = idx - kall * B;
+  const int k = kall % 3;
+  const double stretch = kall >= 3 ? (double)depth : 0.0;
   float o[12] = {0.05f, 0.05f, 0.05f, e0, e0, 0.5f, 0.5f, 0.5f, 0.f, 0.f, 0.f, 1.f};
   if (count[b] > 0) {
     double M[9], half[3], mid[3];
+    const double* V = frame + 9 * (size_t)b;
+    const double z0 = fabs(V[6]), z1 = fabs(V[7]), z2 = fabs(V[8]);
+    const int ja = (z0 >= z1 && z0 >= z2) ? 0 : (z1 >= z2 ? 1 : 2);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int ax = k + j >= 3 ? k + j - 3 : k + j;
@@ -1315,6 +1330,10 @@ __global__ void __launch_bounds__(64) lsq_starts_kernel(int B, int nblk, float e
         const double* src = extents + ((size_t)b * nblk + blk) * 6;
         lo = fmin(lo, src[ax]);
         hi = fmax(hi, src[3 + ax]);
+      }
+      if (ax == ja) {
+        const double grow = stretch * (hi - lo);
+        if (V[6 + ax] > 0.0) lo -= grow; else hi += grow;
       }
       half[j] = 0.5 * (hi - lo);
       mid[j] = 0.5 * (hi + lo);
@@ -1352,7 +1371,7 @@ __global__ void __launch_bounds__(64) lsq_starts_kernel(int B, int nblk, float e
       for (int i = 0; i < 12; ++i) o[i] = c[i];
     }
   }
-  float* dst = starts + ((size_t)k * B + b) * 12;
+  float* dst = starts + ((size_t)kall * B + b) * 12;
 #pragma unroll
   for (int i = 0; i < 12; ++i) dst[i] = o[i];
 }
@@ -1379,6 +1398,132 @@ __global__ void __launch_bounds__(64) lsq_select_kernel(int B, int K, const floa
   for (int i = 0; i < 12; ++i) out_params[12 * (size_t)b + i] = src[i];
   out_energy[b] = be;
   out_index[b] = best;
+}
+
+// -------------------------------------------------------------------------- free-space energy (selection)
+// The point energy sees the image's points only: a model that sticks out where the image says "background",
+// or in front of the visible surface, costs it nothing.  The free-space energy is summed over every resized
+// pixel's ray (x, y) = (c / R, 1 - r / R), least_squares_kernel's pixel rule: along the segment [zlo, kScanZHi]
+// of the ray, zlo = z + margin for a pixel z > 0 (nothing lies in front of the visible surface) and 0 for a
+// pixel <= 0 (the scanner would have seen any surface there), the model must stay outside:
+//   E_fs = a0 a1 a2 sum_pixels min(F(x, y, z*) - 1, 0)^2,  z* = argmin of F over the segment.
+// A NaN pixel and an empty segment (zlo > kScanZHi) add nothing.  f = F^(1/e1) is convex in z (scan_render_kernel's
+// note), so z* is where df/dz changes sign, clipped to the segment: a bisection with a fixed budget on
+// scan_eval's sign, inside the slab |u_i| <= 1 cut with the segment; a ray whose segment misses the slab has
+// F >= 1 there and adds an exact zero without a search (most background pixels).  The minimum is flat in z to
+// second order, so the last bits of an interior z* do not matter (a z* at an end of the segment is that end
+// exactly); the value is the point term's own F: vox_fwd, its zero fix and exp2m1.  A lane that has converged holds its bracket; the loop is left when no lane of the wave is live.
+// grid: (blocks_per_sample, S); sample s reads image s mod Bimg.  partials: [S][nblk] float64 (a lane's term
+// is fp32; lanes summed by DPP, waves in order, blocks in order in free_space_finalize_kernel).
+constexpr int kFsIters = 26;  // a bracket at most 4 wide down to 6e-8
+
+template <int NT>
+__global__ void __launch_bounds__(NT) free_space_kernel(const float* __restrict__ params,
+                                                        const float* __restrict__ target, int Bimg, int H, int W,
+                                                        int R, float margin, double* __restrict__ partials) {
+  __shared__ double red[NT / 64];
+  const int b = blockIdx.y;
+  SQ s;
+  sq_load(params + 12 * (size_t)b, s);
+  const int pix = blockIdx.x * NT + threadIdx.x;
+  bool hit = false;
+  float gx = 0.f, gy = 0.f, z0 = 0.f, z1 = 0.f;
+  RayU ru;
+  if (pix < R * R) {
+    const int r = pix / R, c = pix - r * R;
+    const float sh = (float)H / (float)R, sw = (float)W / (float)R;
+    const int sr = min((int)floorf((float)r * sh), H - 1);
+    const int sc = min((int)floorf((float)c * sw), W - 1);
+    const float z = target[((size_t)(b % Bimg) * H + sr) * W + sc];
+    gx = (float)c / (float)R;
+    gy = 1.f - (float)r / (float)R;
+    z0 = z > 0.f ? z + margin : 0.f;
+    z1 = kScanZHi;
+    hit = z == z && z0 <= z1;
+  }
+  ray_u(s, gx - s.t[0], gy - s.t[1], ru);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {  // the slab, as scan_render_kernel
+    const bool flat = ru.be[i] == 0.f;
+    const float ib = 1.f / (flat ? 1.f : ru.be[i]);
+    const float za = (-1.f - ru.al[i]) * ib, zb = (1.f - ru.al[i]) * ib;
+    hit = hit && !(flat && fabsf(ru.al[i]) > 1.f);
+    z0 = flat ? z0 : fmaxf(z0, fminf(za, zb));
+    z1 = flat ? z1 : fminf(z1, fmaxf(za, zb));
+  }
+  hit = hit && z0 <= z1;
+  float term = 0.f;
+  if (__any(hit)) {
+    float lo = z0, hi = z1;
+    bool live = hit;
+    for (int it = 0; it < kFsIters; ++it) {
+      if (!__any(live)) break;
+      const float mid = 0.5f * (lo + hi);
+      float d;
+      scan_eval(s, ru, mid, d);
+      live = live && mid > lo && mid < hi;
+      if (live) {
+        if (d > 0.f) hi = mid; else lo = mid;  // f rises: the minimum lies below
+      }
+    }
+    if (hit) {
+      // an end of the bracket that never moved is the minimiser itself: the minimum of a segment that starts
+      // behind it lies at the start exactly, where F is not flat (half a last bracket off is a one-sided error)
+      const float zs = lo == z0 ? z0 : (hi == z1 ? z1 : 0.5f * (lo + hi));
+      Vox f;
+      vox_fwd(s, gx - s.t[0], gy - s.t[1], zs - s.t[2], f);
+      const float fm1 = fminf(exp2m1(s.e1 * f.lF), 0.f);
+      term = fm1 * fm1;
+    }
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const double v = wave_sum_d((double)term);
+  if (lane == 0) red[wid] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double acc = 0.0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) acc += red[w];
+    partials[(size_t)b * gridDim.x + blockIdx.x] = acc;
+  }
+}
+
+// One thread per sample: E_fs = a0 a1 a2 * (the blocks' partials in order).  score (nullable) = energy + w E_fs,
+// the multi-start recovery's selection score; w = 0: the energy itself, bitwise, whatever E_fs is.
+__global__ void __launch_bounds__(64) free_space_finalize_kernel(const float* __restrict__ params,
+                                                                 const double* __restrict__ partials, int S, int nblk,
+                                                                 double* __restrict__ energy_fs,
+                                                                 const double* __restrict__ energy, double w,
+                                                                 double* __restrict__ score) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S) return;
+  double acc = 0.0;
+  for (int k = 0; k < nblk; ++k) acc += partials[(size_t)b * nblk + k];
+  const float* p = params + 12 * (size_t)b;
+  const double vol = (double)clampf(p[0], 0.05f, 1.f) * (double)clampf(p[1], 0.05f, 1.f) *
+                     (double)clampf(p[2], 0.05f, 1.f);
+  const double fs = vol * acc;
+  energy_fs[b] = fs;
+  if (score) score[b] = w == 0.0 ? energy[b] : energy[b] + w * fs;
+}
+
+// extra starts [n] floats copied behind the computed ones (a launch, so the chain stays a chain of kernels)
+__global__ void lsq_copy_kernel(const float* __restrict__ src, long long n, float* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+
+// the winner's point energy and free-space energy: row index[b] of [K,B]
+__global__ void __launch_bounds__(64) lsq_gather_kernel(int B, const int* __restrict__ index,
+                                                        const double* __restrict__ energy,
+                                                        const double* __restrict__ energy_fs,
+                                                        double* __restrict__ out_energy,
+                                                        double* __restrict__ out_fs) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const size_t at = (size_t)index[b] * B + b;
+  out_energy[b] = energy[at];
+  out_fs[b] = energy_fs[at];
 }
 
 // -------------------------------------------------------------------------- IoUAccuracy (f64)
@@ -1664,10 +1809,10 @@ extern "C" size_t sqr_least_squares_normal_eq_workspace_bytes(int B, int R) {
 }
 
 // the two launches of the normal equations (arguments checked by the callers)
-static int launch_normal_eq(hipStream_t st, const float* params, const float* target, int B, int H, int W, int R,
-                            double* JtJ, double* Jtr, double* energy, double* energy_copy, double* partials) {
+static int launch_normal_eq(hipStream_t st, const float* params, const float* target, int B, int Bimg, int H, int W,
+                            int R, double* JtJ, double* Jtr, double* energy, double* energy_copy, double* partials) {
   const int nblk = (int)normal_eq_blocks(R);
-  hipLaunchKernelGGL((lsq_normal_eq_kernel<kNeqP>), dim3(nblk, B), dim3(kNeqP), 0, st, params, target, H, W, R,
+  hipLaunchKernelGGL((lsq_normal_eq_kernel<kNeqP>), dim3(nblk, B), dim3(kNeqP), 0, st, params, target, Bimg, H, W, R,
                      partials);
   SQR_HIP_LAUNCH_CHECK("lsq_normal_eq_kernel");
   hipLaunchKernelGGL(lsq_normal_eq_finalize_kernel, dim3(B), dim3(kNeqP), 0, st, params, partials, nblk, JtJ, Jtr,
@@ -1688,7 +1833,7 @@ extern "C" int sqr_least_squares_normal_eq(const float* params, const float* tar
     set_error("least_squares_normal_eq: workspace %zu < %zu bytes", workspace_bytes, need);
     return SQR_E_WORKSPACE;
   }
-  return launch_normal_eq(as_stream(stream), params, target, B, H, W, R, JtJ, Jtr, energy, nullptr,
+  return launch_normal_eq(as_stream(stream), params, target, B, B, H, W, R, JtJ, Jtr, energy, nullptr,
                           (double*)workspace);
 }
 
@@ -1720,6 +1865,43 @@ extern "C" size_t sqr_lsq_lm_refine_workspace_bytes(int B, int R) {
          (size_t)B * 12 * sizeof(float);
 }
 
+// The chain of sqr_lsq_lm_refine over B samples, sample b on image b mod Bimg (arguments checked by the callers;
+// the workspace is sqr_lsq_lm_refine_workspace_bytes(B, R)).  Every sample is on its own and every sum has a
+// fixed order, so a sample's result does not depend on B.
+static int lm_refine_chain(const float* params_in, const float* target, int B, int Bimg, int H, int W, int R, int iters,
+                           double lambda0, double up, double down, float* params_out, double* energy_before,
+                           double* energy_after, int* accepted, void* workspace, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const size_t nb = (size_t)B;
+  double* JtJ = (double*)workspace;
+  double* Jtr = JtJ + 144 * nb;
+  double* lambda = Jtr + 12 * nb;
+  double* JtJ_t = lambda + nb;
+  double* Jtr_t = JtJ_t + 144 * nb;
+  double* E_t = Jtr_t + 12 * nb;
+  double* delta = E_t + nb;
+  double* partials = delta + 12 * nb;
+  float* p_t = (float*)(partials + nb * normal_eq_blocks(R) * kNeqP);
+  hipLaunchKernelGGL(lm_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, params_in, B, lambda0, params_out, lambda,
+                     accepted);
+  SQR_HIP_LAUNCH_CHECK("lm_init_kernel");
+  int rc = launch_normal_eq(st, params_out, target, B, Bimg, H, W, R, JtJ, Jtr, energy_after, energy_before, partials);
+  if (rc != SQR_OK) return rc;
+  for (int it = 0; it <= iters && iters > 0; ++it) {
+    // round it: accept the trial of the round before (none in round 0), solve for the next one and
+    // evaluate it; the last pass only accepts
+    const int accept = it > 0, solve = it < iters;
+    rc = sqr_lsq_lm_step(B, accept, solve, up, down, params_out, JtJ, Jtr, energy_after, lambda, p_t, JtJ_t, Jtr_t,
+                         E_t, delta, accepted, stream);
+    if (rc != SQR_OK) return rc;
+    if (solve) {
+      rc = launch_normal_eq(st, p_t, target, B, Bimg, H, W, R, JtJ_t, Jtr_t, E_t, nullptr, partials);
+      if (rc != SQR_OK) return rc;
+    }
+  }
+  return SQR_OK;
+}
+
 extern "C" int sqr_lsq_lm_refine(const float* params_in, const float* target, int B, int H, int W, int R, int iters,
                                  double lambda0, double up, double down, float* params_out, double* energy_before,
                                  double* energy_after, int* accepted, void* workspace, size_t workspace_bytes,
@@ -1735,35 +1917,28 @@ extern "C" int sqr_lsq_lm_refine(const float* params_in, const float* target, in
                 "lsq_lm_refine: null pointer");
   const size_t need = sqr_lsq_lm_refine_workspace_bytes(B, R);
   SQR_CHECK_ARG(workspace_bytes >= need, "lsq_lm_refine: workspace %zu < %zu bytes", workspace_bytes, need);
-  hipStream_t st = as_stream(stream);
-  const size_t nb = (size_t)B;
-  double* JtJ = (double*)workspace;
-  double* Jtr = JtJ + 144 * nb;
-  double* lambda = Jtr + 12 * nb;
-  double* JtJ_t = lambda + nb;
-  double* Jtr_t = JtJ_t + 144 * nb;
-  double* E_t = Jtr_t + 12 * nb;
-  double* delta = E_t + nb;
-  double* partials = delta + 12 * nb;
-  float* p_t = (float*)(partials + nb * normal_eq_blocks(R) * kNeqP);
-  hipLaunchKernelGGL(lm_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, params_in, B, lambda0, params_out, lambda,
-                     accepted);
-  SQR_HIP_LAUNCH_CHECK("lm_init_kernel");
-  int rc = launch_normal_eq(st, params_out, target, B, H, W, R, JtJ, Jtr, energy_after, energy_before, partials);
-  if (rc != SQR_OK) return rc;
-  for (int it = 0; it <= iters && iters > 0; ++it) {
-    // round it: accept the trial of the round before (none in round 0), solve for the next one and
-    // evaluate it; the last pass only accepts
-    const int accept = it > 0, solve = it < iters;
-    rc = sqr_lsq_lm_step(B, accept, solve, up, down, params_out, JtJ, Jtr, energy_after, lambda, p_t, JtJ_t, Jtr_t,
-                         E_t, delta, accepted, stream);
-    if (rc != SQR_OK) return rc;
-    if (solve) {
-      rc = launch_normal_eq(st, p_t, target, B, H, W, R, JtJ_t, Jtr_t, E_t, nullptr, partials);
-      if (rc != SQR_OK) return rc;
-    }
-  }
-  return SQR_OK;
+  return lm_refine_chain(params_in, target, B, B, H, W, R, iters, lambda0, up, down, params_out, energy_before,
+                         energy_after, accepted, workspace, stream);
+}
+
+extern "C" int sqr_lsq_lm_refine_multi(const float* params_in, const float* target, int K, int B, int H, int W, int R,
+                                       int iters, double lambda0, double up, double down, float* params_out,
+                                       double* energy_before, double* energy_after, int* accepted, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(K >= 1 && B >= 1 && (long long)K * B <= 65535, "lsq_lm_refine_multi: K=%d x B=%d out of range [1,65535]",
+                K, B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "lsq_lm_refine_multi: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "lsq_lm_refine_multi: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(iters >= 0, "lsq_lm_refine_multi: iters=%d must be >= 0", iters);
+  SQR_CHECK_ARG(lambda0 > 0.0, "lsq_lm_refine_multi: lambda0=%g must be > 0", lambda0);
+  SQR_CHECK_ARG(up > 1.0, "lsq_lm_refine_multi: up=%g must be > 1", up);
+  SQR_CHECK_ARG(down > 0.0 && down < 1.0, "lsq_lm_refine_multi: down=%g outside (0,1)", down);
+  SQR_CHECK_ARG(params_in && target && params_out && energy_before && energy_after && accepted && workspace,
+                "lsq_lm_refine_multi: null pointer");
+  const size_t need = sqr_lsq_lm_refine_workspace_bytes(K * B, R);
+  SQR_CHECK_ARG(workspace_bytes >= need, "lsq_lm_refine_multi: workspace %zu < %zu bytes", workspace_bytes, need);
+  return lm_refine_chain(params_in, target, K * B, B, H, W, R, iters, lambda0, up, down, params_out, energy_before,
+                         energy_after, accepted, workspace, stream);
 }
 
 static size_t starts_blocks(int R) { return ((size_t)R * R + 255) / 256; }
@@ -1775,8 +1950,9 @@ extern "C" size_t sqr_lsq_starts_workspace_bytes(int B, int R) {
 }
 
 // the four launches of the starts (arguments checked by the callers)
-static int launch_starts(hipStream_t st, const float* target, int B, int H, int W, int R, float e0, float* starts,
-                         int* count, double* centroid, double* eigenvalues, double* frame, double* workspace) {
+static int launch_starts(hipStream_t st, const float* target, int B, int H, int W, int R, int nsets, float e0,
+                         float depth, float* starts, int* count, double* centroid, double* eigenvalues, double* frame,
+                         double* workspace) {
   const int nblk = (int)starts_blocks(R);
   double* mom = workspace;
   double* ext = mom + (size_t)B * nblk * kMomN;
@@ -1787,8 +1963,8 @@ static int launch_starts(hipStream_t st, const float* target, int B, int H, int 
   SQR_HIP_LAUNCH_CHECK("lsq_frame_kernel");
   hipLaunchKernelGGL((lsq_extents_kernel<256>), dim3(nblk, B), dim3(256), 0, st, target, H, W, R, frame, ext);
   SQR_HIP_LAUNCH_CHECK("lsq_extents_kernel");
-  hipLaunchKernelGGL(lsq_starts_kernel, dim3((3 * B + 63) / 64), dim3(64), 0, st, B, nblk, e0, count, frame, ext,
-                     starts);
+  hipLaunchKernelGGL(lsq_starts_kernel, dim3((3 * nsets * B + 63) / 64), dim3(64), 0, st, B, nblk, nsets, e0, depth,
+                     count, frame, ext, starts);
   SQR_HIP_LAUNCH_CHECK("lsq_starts_kernel");
   return SQR_OK;
 }
@@ -1804,8 +1980,24 @@ extern "C" int sqr_lsq_starts(const float* target, int B, int H, int W, int R, f
                 "lsq_starts: null pointer");
   const size_t need = sqr_lsq_starts_workspace_bytes(B, R);
   SQR_CHECK_ARG(workspace_bytes >= need, "lsq_starts: workspace %zu < %zu bytes", workspace_bytes, need);
-  return launch_starts(as_stream(stream), target, B, H, W, R, e0, starts, count, centroid, eigenvalues, frame,
+  return launch_starts(as_stream(stream), target, B, H, W, R, 1, e0, 0.f, starts, count, centroid, eigenvalues, frame,
                        (double*)workspace);
+}
+
+extern "C" int sqr_lsq_starts6(const float* target, int B, int H, int W, int R, float e0, float depth, float* starts,
+                               int* count, double* centroid, double* eigenvalues, double* frame, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(B >= 1 && B <= 65535, "lsq_starts6: B=%d out of range [1,65535]", B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "lsq_starts6: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "lsq_starts6: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(e0 >= 0.1f && e0 <= 1.f, "lsq_starts6: e0=%g outside [0.1,1]", (double)e0);
+  SQR_CHECK_ARG(depth >= 0.f && depth <= 8.f, "lsq_starts6: depth=%g outside [0,8]", (double)depth);
+  SQR_CHECK_ARG(target && starts && count && centroid && eigenvalues && frame && workspace,
+                "lsq_starts6: null pointer");
+  const size_t need = sqr_lsq_starts_workspace_bytes(B, R);
+  SQR_CHECK_ARG(workspace_bytes >= need, "lsq_starts6: workspace %zu < %zu bytes", workspace_bytes, need);
+  return launch_starts(as_stream(stream), target, B, H, W, R, 2, e0, depth, starts, count, centroid, eigenvalues,
+                       frame, (double*)workspace);
 }
 
 extern "C" int sqr_lsq_select(int B, int K, const float* params, const double* energy, float* out_params,
@@ -1859,7 +2051,8 @@ extern "C" int sqr_lsq_recover(const float* target, int B, int H, int W, int R, 
   char* region = (char*)(frame + 9 * nb);
   float* starts = (float*)(region + recover_region_bytes(B, R));
   int* count = (int*)(starts + 3 * 12 * nb);
-  int rc = launch_starts(st, target, B, H, W, R, e0, starts, count, centroid, eigenvalues, frame, (double*)region);
+  int rc = launch_starts(st, target, B, H, W, R, 1, e0, 0.f, starts, count, centroid, eigenvalues, frame,
+                         (double*)region);
   if (rc != SQR_OK) return rc;
   // the three refinements one after the other on the stream, each in the same region
   for (int k = 0; k < 3; ++k) {
@@ -1869,6 +2062,113 @@ extern "C" int sqr_lsq_recover(const float* target, int B, int H, int W, int R, 
     if (rc != SQR_OK) return rc;
   }
   return sqr_lsq_select(B, 3, all_params, all_after, params_out, energy_out, index_out, stream);
+}
+
+static size_t free_space_blocks(int R) { return ((size_t)R * R + 255) / 256; }
+
+extern "C" size_t sqr_lsq_free_space_workspace_bytes(int S, int R) {
+  if (S <= 0 || R <= 0) return 0;
+  return (size_t)S * free_space_blocks(R) * sizeof(double);
+}
+
+// the two launches of the free-space energy (arguments checked by the callers)
+static int launch_free_space(hipStream_t st, const float* params, const float* target, int S, int B, int H, int W,
+                             int R, float margin, double* energy_fs, const double* energy, double w, double* score,
+                             double* partials) {
+  const int nblk = (int)free_space_blocks(R);
+  hipLaunchKernelGGL((free_space_kernel<256>), dim3(nblk, S), dim3(256), 0, st, params, target, B, H, W, R, margin,
+                     partials);
+  SQR_HIP_LAUNCH_CHECK("free_space_kernel");
+  hipLaunchKernelGGL(free_space_finalize_kernel, dim3((S + 63) / 64), dim3(64), 0, st, params, partials, S, nblk,
+                     energy_fs, energy, w, score);
+  SQR_HIP_LAUNCH_CHECK("free_space_finalize_kernel");
+  return SQR_OK;
+}
+
+extern "C" int sqr_lsq_free_space(const float* params, const float* target, int S, int B, int H, int W, int R,
+                                  float margin, double* energy_fs, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  SQR_CHECK_ARG(B >= 1 && S >= B && S <= 65535 && S % B == 0,
+                "lsq_free_space: S=%d must be a multiple of B=%d in [B,65535]", S, B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "lsq_free_space: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "lsq_free_space: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(margin >= 0.f, "lsq_free_space: margin=%g must be >= 0", (double)margin);
+  SQR_CHECK_ARG(params && target && energy_fs && workspace, "lsq_free_space: null pointer");
+  const size_t need = sqr_lsq_free_space_workspace_bytes(S, R);
+  SQR_CHECK_ARG(workspace_bytes >= need, "lsq_free_space: workspace %zu < %zu bytes", workspace_bytes, need);
+  return launch_free_space(as_stream(stream), params, target, S, B, H, W, R, margin, energy_fs, nullptr, 0.0, nullptr,
+                           (double*)workspace);
+}
+
+// float64 first: [centroid 3][eigenvalues 3][frame 9] per image, then one region that the starts' partials, the
+// batched refinement and the free-space partials use in turn, then count [B] i32
+static size_t recover_multi_region_bytes(int K, int B, int R) {
+  size_t m = sqr_lsq_starts_workspace_bytes(B, R);
+  const size_t b = sqr_lsq_lm_refine_workspace_bytes(K * B, R), c = sqr_lsq_free_space_workspace_bytes(K * B, R);
+  m = b > m ? b : m;
+  return c > m ? c : m;
+}
+
+extern "C" size_t sqr_lsq_recover_multi_workspace_bytes(int K, int B, int R) {
+  if (K <= 0 || B <= 0 || R <= 0) return 0;
+  return (size_t)B * kRecoverDoubles * sizeof(double) + recover_multi_region_bytes(K, B, R) + (size_t)B * sizeof(int);
+}
+
+extern "C" int sqr_lsq_recover_multi(const float* target, int B, int H, int W, int R, int iters, int nstarts, float e0,
+                                     float depth, const float* extra, int Kx, double lambda0, double up, double down,
+                                     double w_fs, float margin, float* params_out, double* energy_out,
+                                     double* energy_fs_out, int* index_out, float* all_starts, float* all_params,
+                                     double* all_before, double* all_after, double* all_fs, double* all_score,
+                                     int* all_accepted, void* workspace, size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(nstarts == 3 || nstarts == 6, "lsq_recover_multi: nstarts=%d must be 3 or 6", nstarts);
+  SQR_CHECK_ARG(Kx >= 0 && (Kx == 0 || extra), "lsq_recover_multi: Kx=%d extra starts without a pointer", Kx);
+  const long long K = (long long)nstarts + Kx;
+  SQR_CHECK_ARG(B >= 1 && K * B <= 65535, "lsq_recover_multi: K=%lld x B=%d out of range [1,65535]", K, B);
+  SQR_CHECK_ARG(R >= 1 && R <= 1024, "lsq_recover_multi: R=%d out of range [1,1024]", R);
+  SQR_CHECK_ARG(H >= 1 && W >= 1, "lsq_recover_multi: bad target size %dx%d", H, W);
+  SQR_CHECK_ARG(iters >= 0, "lsq_recover_multi: iters=%d must be >= 0", iters);
+  SQR_CHECK_ARG(e0 >= 0.1f && e0 <= 1.f, "lsq_recover_multi: e0=%g outside [0.1,1]", (double)e0);
+  SQR_CHECK_ARG(depth >= 0.f && depth <= 8.f, "lsq_recover_multi: depth=%g outside [0,8]", (double)depth);
+  SQR_CHECK_ARG(lambda0 > 0.0, "lsq_recover_multi: lambda0=%g must be > 0", lambda0);
+  SQR_CHECK_ARG(up > 1.0, "lsq_recover_multi: up=%g must be > 1", up);
+  SQR_CHECK_ARG(down > 0.0 && down < 1.0, "lsq_recover_multi: down=%g outside (0,1)", down);
+  SQR_CHECK_ARG(w_fs >= 0.0 && w_fs <= 1e300, "lsq_recover_multi: w_fs=%g must be a finite number >= 0", w_fs);
+  SQR_CHECK_ARG(margin >= 0.f, "lsq_recover_multi: margin=%g must be >= 0", (double)margin);
+  SQR_CHECK_ARG(target && params_out && energy_out && energy_fs_out && index_out && all_starts && all_params &&
+                    all_before && all_after && all_fs && all_score && all_accepted && workspace,
+                "lsq_recover_multi: null pointer");
+  const int Kall = (int)K;
+  const size_t need = sqr_lsq_recover_multi_workspace_bytes(Kall, B, R);
+  SQR_CHECK_ARG(workspace_bytes >= need, "lsq_recover_multi: workspace %zu < %zu bytes", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  const size_t nb = (size_t)B;
+  double* centroid = (double*)workspace;
+  double* eigenvalues = centroid + 3 * nb;
+  double* frame = eigenvalues + 3 * nb;
+  char* region = (char*)(frame + 9 * nb);
+  int* count = (int*)(region + recover_multi_region_bytes(Kall, B, R));
+  int rc = launch_starts(st, target, B, H, W, R, nstarts / 3, e0, depth, all_starts, count, centroid, eigenvalues,
+                         frame, (double*)region);
+  if (rc != SQR_OK) return rc;
+  if (Kx > 0) {
+    const long long n = (long long)Kx * B * 12;
+    hipLaunchKernelGGL(lsq_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, extra, n,
+                       all_starts + 12 * nb * nstarts);
+    SQR_HIP_LAUNCH_CHECK("lsq_copy_kernel");
+  }
+  rc = lm_refine_chain(all_starts, target, Kall * B, B, H, W, R, iters, lambda0, up, down, all_params, all_before,
+                       all_after, all_accepted, region, stream);
+  if (rc != SQR_OK) return rc;
+  rc = launch_free_space(st, all_params, target, Kall * B, B, H, W, R, margin, all_fs, all_after, w_fs, all_score,
+                         (double*)region);
+  if (rc != SQR_OK) return rc;
+  // the winning score goes to energy_out first; the gather puts the winner's point energy there
+  rc = sqr_lsq_select(B, Kall, all_params, all_score, params_out, energy_out, index_out, stream);
+  if (rc != SQR_OK) return rc;
+  hipLaunchKernelGGL(lsq_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, index_out, all_after, all_fs,
+                     energy_out, energy_fs_out);
+  SQR_HIP_LAUNCH_CHECK("lsq_gather_kernel");
+  return SQR_OK;
 }
 
 template <typename P>

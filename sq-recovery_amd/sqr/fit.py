@@ -10,12 +10,13 @@ visible points — not a higher IoU against a label: the depth image shows one s
 
 Everything runs on the device (Adam: sqr_least_squares_fwd_bwd per step plus a handful of elementwise
 launches on the [B,12] tensor; LM: sqr_lsq_lm_refine, one chain of normal-equations and step kernels;
-recover: sqr_lsq_recover, the starts' four launches, three such chains and a selection);
+recover: sqr_lsq_recover, the starts' four launches, three such chains and a selection, or
+sqr_lsq_recover_multi, every start in one such chain, a free-space evaluation and a scored selection);
 nothing is read back inside the loop.
 """
 import torch
 
-from .losses import least_squares, lm_refine, lsq_recover, lsq_starts
+from .losses import least_squares, lm_refine, lsq_recover, lsq_recover_multi, lsq_starts
 
 
 def refine_lm(images, params, iters=10, render_size=32, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
@@ -32,10 +33,11 @@ def refine_lm(images, params, iters=10, render_size=32, lambda0=1e-3, up=10.0, d
     return (out, before, after, accepted) if return_info else (out, before, after)
 
 
-def recover(images, iters=30, render_size=32, e0=1.0, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
+def recover(images, iters=30, render_size=32, e0=1.0, lambda0=1e-3, up=10.0, down=0.1, return_info=False,
+            starts="classic", depth=1.0, free_space=0.0, margin=1.0 / 255.0, extra_starts=None):
     """images [B,1,H,W] or [B,H,W] (CUDA) -> (params [B,12] f32, energy [B] f64, start_index [B] i32), with
-    return_info also a dict: params [3,B,12], energy_before [3,B], energy_after [3,B], accepted [3,B] of every
-    start, the starts themselves [3,B,12] and the moments (count, centroid, eigenvalues, frame).
+    return_info also a dict: params [K,B,12], energy_before [K,B], energy_after [K,B], accepted [K,B] of every
+    start, the starts themselves [K,B,12] and the moments (count, centroid, eigenvalues, frame).
 
     Solina & Bajcsy's recovery, no network and no label: the centre of gravity and the principal axes of the
     image's points give position and orientation, the extents along those axes the sizes, an ellipsoid
@@ -48,17 +50,39 @@ def recover(images, iters=30, render_size=32, e0=1.0, lambda0=1e-3, up=10.0, dow
     energy 0.  Every sample is recovered on its own; no host wait, so the call can be captured in a HIP
     graph.
 
+    The defaults (starts="classic", free_space=0, no extra_starts) are that call, sqr_lsq_recover.  Anything
+    else goes through sqr_lsq_recover_multi, one chain over all K B samples:
+      starts="depth"   six starts, K = 6: the three above and three whose extent along the frame axis nearest
+                       the viewing direction is stretched by `depth` times itself away from the viewer (the
+                       image shows the front half of the body only: lsq_starts6)
+      free_space=w     the winner is the lowest score = energy + w * free-space energy (free_space_energy with
+                       `margin`): a model that fits the points but occupies space the image shows to be empty
+                       loses.  `energy` stays the winner's point energy.
+      extra_starts     [B,12] or [Kx,B,12] more starts behind the computed ones (a network's prediction, for
+                       instance); start_index counts them from 3 or 6 on.
+    With return_info the dict then also holds energy_fs [K,B], score [K,B] and the winner's energy_fs [B] under
+    "winner_energy_fs".
+
     return_info costs a second run of the starts (sqr_lsq_starts: four more short launches and five small
-    allocations): sqr_lsq_recover keeps the starts it refines in its workspace, whose layout is not part of its
-    interface.  The starts' kernels are bitwise reproducible, so the starts and moments returned are exactly
-    the ones that were refined."""
+    allocations) for the moments: the recovery keeps them in its workspace, whose layout is not part of its
+    interface.  The starts' kernels are bitwise reproducible, so the moments returned are exactly the ones
+    that were used."""
     R = int(render_size)
-    out, energy, index, allp, before, after, accepted = lsq_recover(images, R, int(iters), e0, lambda0, up, down)
+    if starts not in ("classic", "depth"):
+        raise ValueError("recover: starts must be 'classic' or 'depth', got %r" % (starts,))
+    if starts == "classic" and float(free_space) == 0.0 and extra_starts is None:
+        out, energy, index, allp, before, after, accepted = lsq_recover(images, R, int(iters), e0, lambda0, up, down)
+        if not return_info:
+            return out, energy, index
+        st, info = lsq_starts(images, R, e0)
+        info = dict(info, params=allp, energy_before=before, energy_after=after, accepted=accepted, starts=st)
+        return out, energy, index, info
+    out, energy, fs, index, multi = lsq_recover_multi(images, R, int(iters), 6 if starts == "depth" else 3, e0, depth,
+                                                      extra_starts, lambda0, up, down, free_space, margin)
     if not return_info:
         return out, energy, index
-    starts, info = lsq_starts(images, R, e0)
-    info = dict(info, params=allp, energy_before=before, energy_after=after, accepted=accepted, starts=starts)
-    return out, energy, index, info
+    _, info = lsq_starts(images, R, e0)
+    return out, energy, index, dict(info, winner_energy_fs=fs, **multi)
 
 
 def refine(images, params, steps=200, lr=2e-3, render_size=32, betas=(0.9, 0.999), eps=1e-8, method="adam"):

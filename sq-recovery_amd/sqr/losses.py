@@ -278,6 +278,109 @@ def lsq_recover(target, R, iters, e0, lambda0, up, down):
     return out, energy, index, allp, before, after, accepted
 
 
+def _stacked_params(params, B, what):
+    """[K,B,12] (or [B,12] = one slice) CUDA parameters as contiguous float32 [K,B,12]."""
+    _require_cuda(params)
+    p = params.detach().to(torch.float32)
+    if p.dim() == 2:
+        p = p[None]
+    if p.dim() != 3 or p.shape[0] < 1 or p.shape[1] != B or p.shape[2] != 12:
+        raise ValueError("%s must be [K,%d,12] or [%d,12], got %s" % (what, B, B, tuple(params.shape)))
+    return p.contiguous()
+
+
+def free_space_energy(images, params, render_size, margin=1.0 / 255.0):
+    """sqr_lsq_free_space -> E_fs [S] f64 (no autograd): images [B,1,H,W] or [B,H,W], params [S,12] with S a
+    multiple of B, sample s against image s mod B (a [K,B,12] stack flattened).  Along every resized pixel's ray
+    the model must stay out of the space the image shows to be empty: in front of the visible surface (from
+    z + margin on; one grey level by default, a quantised pixel lies up to one level below the true surface)
+    and, on a background pixel, everywhere from z = 0 on.  E_fs = a0 a1 a2 sum_pixels min(min_z F - 1, 0)^2.
+    Bitwise reproducible, a sample's value independent of the batch; two launches, no host wait."""
+    t, B, H, W = _image_only(images)
+    _require_cuda(params)
+    if params.dim() != 2 or params.shape[1] != 12 or params.shape[0] < B or params.shape[0] % B:
+        raise ValueError("params must be [S,12] with S a multiple of the %d images, got %s" % (B, tuple(params.shape)))
+    p = params.detach().to(torch.float32).contiguous()
+    S = int(p.shape[0])
+    out = torch.empty(S, dtype=torch.float64, device=p.device)
+    L = lib()
+    wsb = L.sqr_lsq_free_space_workspace_bytes(S, int(render_size))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+    check(L.sqr_lsq_free_space(ptr(p), ptr(t), S, B, H, W, int(render_size), float(margin), ptr(out), ptr(ws), wsb,
+                               stream_ptr(p.device)), "sqr_lsq_free_space")
+    return out
+
+
+def lm_refine_multi(target, params, R, iters, lambda0, up, down):
+    """sqr_lsq_lm_refine_multi: params [K,B,12], target [B,1,H,W] or [B,H,W] -> (params [K,B,12] f32,
+    energy_before [K,B] f64, energy_after [K,B] f64, accepted [K,B] i32), bitwise what K lm_refine calls on the
+    slices return.  One chain of launches over the K B samples on the current stream; no host wait."""
+    t, B, H, W = _image_only(target)
+    p = _stacked_params(params, B, "params")
+    K, dev = int(p.shape[0]), p.device
+    out = torch.empty(K, B, 12, dtype=torch.float32, device=dev)
+    before = torch.empty(K, B, dtype=torch.float64, device=dev)
+    after = torch.empty(K, B, dtype=torch.float64, device=dev)
+    accepted = torch.empty(K, B, dtype=torch.int32, device=dev)
+    L = lib()
+    wsb = L.sqr_lsq_lm_refine_workspace_bytes(K * B, int(R))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(L.sqr_lsq_lm_refine_multi(ptr(p), ptr(t), K, B, H, W, int(R), int(iters), float(lambda0), float(up),
+                                    float(down), ptr(out), ptr(before), ptr(after), ptr(accepted), ptr(ws), wsb,
+                                    stream_ptr(dev)), "sqr_lsq_lm_refine_multi")
+    return out, before, after, accepted
+
+
+def lsq_starts6(target, R, e0=1.0, depth=1.0):
+    """sqr_lsq_starts6 -> (starts [6,B,12] f32, info as lsq_starts): lsq_starts' three starts, bitwise, and
+    three more whose extent along the frame axis nearest the viewing direction is stretched by depth times
+    itself away from the viewer (a depth image shows the front half only).  depth = 0 repeats starts 0..2."""
+    t, B, H, W = _image_only(target)
+    dev = t.device
+    starts = torch.empty(6, B, 12, dtype=torch.float32, device=dev)
+    info = {"count": torch.empty(B, dtype=torch.int32, device=dev),
+            "centroid": torch.empty(B, 3, dtype=torch.float64, device=dev),
+            "eigenvalues": torch.empty(B, 3, dtype=torch.float64, device=dev),
+            "frame": torch.empty(B, 3, 3, dtype=torch.float64, device=dev)}
+    L = lib()
+    wsb = L.sqr_lsq_starts_workspace_bytes(B, int(R))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(L.sqr_lsq_starts6(ptr(t), B, H, W, int(R), float(e0), float(depth), ptr(starts), ptr(info["count"]),
+                            ptr(info["centroid"]), ptr(info["eigenvalues"]), ptr(info["frame"]), ptr(ws), wsb,
+                            stream_ptr(dev)), "sqr_lsq_starts6")
+    return starts, info
+
+
+def lsq_recover_multi(target, R, iters, nstarts, e0, depth, extra, lambda0, up, down, w_fs, margin):
+    """sqr_lsq_recover_multi -> (params [B,12] f32, energy [B] f64, energy_fs [B] f64, index [B] i32, info dict:
+    starts, params [K,B,12] f32, energy_before, energy_after, energy_fs, score [K,B] f64, accepted [K,B] i32),
+    K = nstarts (3 or 6) + the extra starts ([Kx,B,12] or [B,12] or None).  One chain of launches on the current
+    stream; no host wait."""
+    t, B, H, W = _image_only(target)
+    dev = t.device
+    x = _stacked_params(extra, B, "extra_starts") if extra is not None else None
+    Kx = int(x.shape[0]) if x is not None else 0
+    K = int(nstarts) + Kx
+    f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)  # noqa: E731
+    out = torch.empty(B, 12, dtype=torch.float32, device=dev)
+    energy, fs = f64(B), f64(B)
+    index = torch.empty(B, dtype=torch.int32, device=dev)
+    info = {"starts": torch.empty(K, B, 12, dtype=torch.float32, device=dev),
+            "params": torch.empty(K, B, 12, dtype=torch.float32, device=dev),
+            "energy_before": f64(K, B), "energy_after": f64(K, B), "energy_fs": f64(K, B), "score": f64(K, B),
+            "accepted": torch.empty(K, B, dtype=torch.int32, device=dev)}
+    L = lib()
+    wsb = L.sqr_lsq_recover_multi_workspace_bytes(K, B, int(R))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(L.sqr_lsq_recover_multi(ptr(t), B, H, W, int(R), int(iters), int(nstarts), float(e0), float(depth), ptr(x),
+                                  Kx, float(lambda0), float(up), float(down), float(w_fs), float(margin), ptr(out),
+                                  ptr(energy), ptr(fs), ptr(index), ptr(info["starts"]), ptr(info["params"]),
+                                  ptr(info["energy_before"]), ptr(info["energy_after"]), ptr(info["energy_fs"]),
+                                  ptr(info["score"]), ptr(info["accepted"]), ptr(ws), wsb, stream_ptr(dev)),
+          "sqr_lsq_recover_multi")
+    return out, energy, fs, index, info
+
+
 def implicit_render(params, R, tau=1.0, sharpness=100.0):
     """depth_projection (classes.py:232-282) -> [B,R,R] float32 images (no autograd)."""
     _require_cuda(params)

@@ -16,6 +16,10 @@ of the projected prediction (a, e, t clamped, q normalised) and the result is a 
 alone (sqr.fit.recover: Solina & Bajcsy's start from the points' moments, --classical-iters
 Levenberg-Marquardt iterations from each of three axis orders, the lowest energy wins) and printed in the
 same format with that energy and the winning start.  It composes with --refine.
+--starts depth adds three depth-aware starts (the extent along the viewing direction doubled away from the viewer:
+the image shows the front half only) and refines all six as one batch; --free-space W picks the winner by
+energy + W x the free-space energy (a model must not occupy space the image shows to be empty).  With
+--classical-starts (and a --model checkpoint) the network's prediction competes as one more start.
 """
 import argparse
 import os
@@ -54,16 +58,40 @@ def main(argv=None):
                          "(sqr.fit.recover, CUDA)")
     ap.add_argument("--classical-iters", type=int, default=30, metavar="N",
                     help="Levenberg-Marquardt iterations per start of --classical")
+    ap.add_argument("--starts", choices=("classic", "depth"), default="classic",
+                    help="--classical: the three starts, or those and three depth-aware ones")
+    ap.add_argument("--free-space", type=float, default=0.0, metavar="W",
+                    help="--classical: select by energy + W x free-space energy")
+    ap.add_argument("--classical-starts", action="store_true",
+                    help="run the network and the classical recovery together: the prediction is one more start")
     args = ap.parse_args(argv)
 
     img = read_image_gray(args.image)
     if args.classical:
         from sqr.fit import recover
         x = torch.from_numpy(img.astype(np.float32)[None, None] / 255).to(args.device)
-        pred, energy, start = recover(x, iters=args.classical_iters)
+        pred, energy, start = recover(x, iters=args.classical_iters, starts=args.starts, free_space=args.free_space)
         a, e, t, q = (o.cpu().numpy() for o in torch.split(pred, (3, 2, 3, 4), dim=1))
         print("Recovered parameters (classical, %d Levenberg-Marquardt iterations per start, LeastSquares energy "
               "%.6g, start %d): " % (args.classical_iters, energy.item(), start.item()))
+    elif args.classical_starts:
+        from sqr.fit import recover
+        net = ResNetSQ(outputs=4, pretrained=False).to(args.device)
+        if os.path.exists(args.model):
+            _, net, _, _ = load_model(args.model, net, None)
+        else:
+            print("checkpoint %s not found: using random weights" % args.model)
+        net.eval()
+        x = torch.from_numpy(img.astype(np.float32)[None, None] / 255).to(args.device)
+        guess = torch.from_numpy(np.concatenate(predict(net, img, args.device), 1)).to(args.device)
+        pred, energy, start = recover(x, iters=args.classical_iters, starts=args.starts, free_space=args.free_space,
+                                      extra_starts=guess)
+        nown = 6 if args.starts == "depth" else 3
+        a, e, t, q = (o.cpu().numpy() for o in torch.split(pred, (3, 2, 3, 4), dim=1))
+        print("Recovered parameters (classical starts and the prediction, %d Levenberg-Marquardt iterations per "
+              "start, LeastSquares energy %.6g, start %d%s): " % (
+                  args.classical_iters, energy.item(), start.item(),
+                  " = the prediction" if start.item() == nown else ""))
     else:
         net = ResNetSQ(outputs=4, pretrained=False).to(args.device)
         if os.path.exists(args.model):

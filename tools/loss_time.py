@@ -20,6 +20,13 @@ times the classical recovery (sqr.fit.recover, 30 iterations per start) at the s
 a replayed graph, next to its starts alone and to one sqr.fit.refine_lm with the same iterations in the same
 process, and reports the energies, the winning starts and the IoU against the labels of that batch.
 
+    python tools/loss_time.py recover-multi
+
+times the six-start scored recovery (sqr.fit.recover with starts="depth", free_space=1) and free_space_energy
+alone on that batch, eagerly and inside a replayed graph, next to today's three-start recover, to three starts
+through the batched chain and to the batched refinement against three separate ones, in the same process, and
+reports the IoU of the three-start and of the six-start scored winners.
+
     python tools/loss_time.py scan
 
 times the scanner-style depth render (sqr_scan_render) at B = 256, S = 256, eagerly and inside a replayed
@@ -153,6 +160,48 @@ def recover(dev, R=64, H=256, B=64, iters=30):
     return res
 
 
+def recover_multi(dev, R=64, H=256, B=64, iters=30):
+    """The recover mode's batch: sqr.fit.recover as it was, three starts through the batched chain, the six-start
+    scored recovery, free_space_energy of the six results, and lm_refine_multi over 3 B samples against three
+    refine_lm calls of B."""
+    from sqr import fit
+    p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
+    img = losses.scan_render(p, H, 255).unsqueeze(1).contiguous()
+    kw = dict(iters=iters, render_size=R)
+    six = lambda: fit.recover(img, starts="depth", free_space=1.0, **kw)  # noqa: E731
+    three_multi = lambda: fit.recover(img, starts="classic", free_space=1.0, **kw)  # noqa: E731
+    out6, e6, i6, info = fit.recover(img, starts="depth", free_space=1.0, return_info=True, **kw)
+    flat = info["params"].reshape(-1, 12).contiguous()
+    st3 = info["starts"][:3].contiguous()
+
+    def three_refines():
+        for k in range(3):
+            fit.refine_lm(img, st3[k], **kw)
+
+    res = {"shape": "R%d_H%d_B%d" % (R, H, B), "iters": iters,
+           "recover_eager_ms": round(_eager_ms(lambda: fit.recover(img, **kw)), 4),
+           "recover_in_graph_us": round(_graph_us(lambda: fit.recover(img, **kw)), 2),
+           "recover_3_batched_scored_eager_ms": round(_eager_ms(three_multi), 4),
+           "recover_3_batched_scored_in_graph_us": round(_graph_us(three_multi), 2),
+           "recover_6_scored_eager_ms": round(_eager_ms(six), 4),
+           "recover_6_scored_in_graph_us": round(_graph_us(six), 2),
+           "free_space_6B_eager_ms": round(_eager_ms(lambda: losses.free_space_energy(img, flat, R)), 4),
+           "free_space_6B_in_graph_us": round(_graph_us(lambda: losses.free_space_energy(img, flat, R)), 2),
+           "refine_3_separate_in_graph_us": round(_graph_us(three_refines), 2),
+           "refine_3_batched_in_graph_us": round(_graph_us(
+               lambda: losses.lm_refine_multi(img, st3, R, iters, 1e-3, 10.0, 0.1)), 2)}
+    res["recover_6_over_recover_in_graph"] = round(res["recover_6_scored_in_graph_us"] / res["recover_in_graph_us"], 3)
+    acc = classes.IoUAccuracy(64, dev, reduce=False)
+    out3 = fit.recover(img, **kw)[0]
+    for name, out in (("recover", out3), ("recover_6_scored", out6)):
+        iou = acc(p, out)
+        res[name + "_iou64_mean"] = round(iou.mean().item(), 4)
+        res[name + "_iou64_share_above_0.9"] = round((iou >= 0.9).double().mean().item(), 4)
+    res["winning_start_counts"] = torch.bincount(i6.long(), minlength=6).tolist()
+    res["energy_mean"] = {"point": e6.mean().item(), "free_space": info["winner_energy_fs"].mean().item()}
+    return res
+
+
 def scan(dev, S=256, B=256, host_images=16):
     from sqr import cpu
     p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
@@ -181,6 +230,10 @@ def main():
     out = {"env": {k: v for k, v in os.environ.items() if k.startswith("SQR_")}}
     if sys.argv[1:] == ["scan"]:
         out["scan"] = scan(dev)
+        print(json.dumps(out))
+        return
+    if sys.argv[1:] == ["recover-multi"]:
+        out["recover_multi"] = recover_multi(dev)
         print(json.dumps(out))
         return
     if sys.argv[1:] == ["recover"]:
