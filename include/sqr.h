@@ -18,6 +18,9 @@
  *   sqr_implicit_render        torch/classes.py:232-282  ImplicitLoss.depth_projection (forward only)
  *   sqr_scan_render            no counterpart in torch/: the `data/scanner` binary behind helpers.py:27-39
  *                              (the hard orthographic depth map the datasets' images are)
+ *   sqr_sq_sample, sqr_sq_stream_advance
+ *                              no counterpart in torch/: the label distribution of gen_rand_rot.py:21-31 drawn
+ *                              on the device from a position kept in device memory
  *   sqr_explicit_loss_fwd_bwd  torch/classes.py:109-201  ExplicitLoss (occupancy :138-189, __call__ :191-201)
  *   sqr_least_squares_fwd_bwd  torch/classes.py:297-371  LeastSquares (energy_function :318-356, __call__
  *                              :358-371) + its autograd backward (analytic here)
@@ -127,6 +130,28 @@ int sqr_implicit_render(const float* params, int B, int R, float tau, float shar
  * One thread per pixel, no atomics: bitwise reproducible.  1 <= B <= 65535, 2 <= S <= 8192,
  * 0 <= levels <= 2^24. */
 int sqr_scan_render(const float* params, int B, int S, int levels, float* images, void* stream);
+
+/* On-device label sampler: params [B,12] f32 in the normalised layout [a(3), e(2), t(3), q(4)], drawn from
+ * the distribution of classes.sample_sq_params by a counter-based generator.  Sample number i of substream s
+ * under seed k is a pure function of (k, s, i):
+ *   bits      Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85; one
+ *             round maps (c0,c1,c2,c3) to (hi(M1 c2)^c1^k0, lo(M1 c2), hi(M0 c0)^c3^k1, lo(M0 c0)), the key
+ *             advancing by the Weyl constants after each round), called three times per sample, call = 0, 1, 2,
+ *             with counter (i_lo, i_hi, call, s) and key (k_lo, k_hi); the twelve words are w[4 call + j];
+ *   uniforms  u_j = (w_j >> 8) 2^-24, exact in f32, in [0, 1);
+ *   labels    a_i = (25 + 50 u_i) / 255, e_i = 0.1 + 0.9 u_{3+i}, t_i = (88 + 80 u_{5+i}) / 255,
+ *             q = (sqrt(1-u8) sin 2pi u9, sqrt(1-u8) cos 2pi u9, sqrt(u8) sin 2pi u10, sqrt(u8) cos 2pi u10);
+ *             w_11 is unused.
+ * Row b of a call is sample *position + offset + b (64-bit, wrapping): `position` is a DEVICE uint64 the
+ * kernel reads, never a kernel argument, so a captured graph that also holds sqr_sq_stream_advance draws
+ * new samples at every replay.  raw (nullable) [B,12] u32 receives the words w.  One thread per sample, no
+ * atomics: bitwise reproducible.  1 <= B <= 65535. */
+int sqr_sq_sample(const uint64_t* position, uint64_t seed, uint32_t substream, uint64_t offset, int B,
+                  float* params, uint32_t* raw, void* stream);
+
+/* *position += stride by one thread (an ordinary load and store, no atomics): stream order has retired every
+ * earlier read of the old value, and every later sqr_sq_sample on the stream sees the new one. */
+int sqr_sq_stream_advance(uint64_t* position, uint64_t stride, void* stream);
 
 size_t sqr_explicit_loss_workspace_bytes(int B, int R);
 

@@ -40,13 +40,17 @@ def _unwrap(model):
     return model.module if hasattr(model, "module") and isinstance(model.module, torch.nn.Module) else model
 
 
-def save_model(path, epoch, model, optimizer, loss, scaler=None):
+def save_model(path, epoch, model, optimizer, loss, scaler=None, source=None):
     """helpers.py:42-48.  scaler (optional, fp16 runs): its state_dict goes under the extra key
-    'scaler_state_dict' — the reference's four keys are unchanged, so either side loads the file."""
+    'scaler_state_dict' — the reference's four keys are unchanged, so either side loads the file.
+    source (optional, --online runs): the training stream's {seed, substream, position} (sqr.data.OnlineSource)
+    goes under the extra key 'stream_state' in the same way."""
     ck = {"epoch": epoch, "model_state_dict": _unwrap(model).state_dict(),
           "optimizer_state_dict": optimizer.state_dict(), "loss": loss}
     if scaler is not None:
         ck["scaler_state_dict"] = scaler.state_dict()
+    if source is not None:
+        ck["stream_state"] = source.state_dict()
     torch.save(ck, path)
 
 
@@ -60,10 +64,11 @@ def _safe_load(path, map_location):
             return torch.load(path, map_location=map_location, weights_only=True)
 
 
-def load_model(path, model, optimizer, plot=False, scaler=None):
+def load_model(path, model, optimizer, plot=False, scaler=None, source=None):
     """helpers.py:51-68 (map_location cuda:0 when a GPU is present, as the reference).  scaler
     (optional): restored from 'scaler_state_dict' when the checkpoint has it (a resumed fp16 run
-    keeps its loss scale and growth tracker)."""
+    keeps its loss scale and growth tracker).  source (optional): restored from 'stream_state' when the
+    checkpoint has it (a resumed --online run goes on at the saved position)."""
     print("Loading model: " + path)
     dev = "cuda:0" if torch.cuda.is_available() else "cpu"
     checkpoint = _safe_load(path, dev)
@@ -72,6 +77,8 @@ def load_model(path, model, optimizer, plot=False, scaler=None):
         optimizer.load_state_dict(checkpoint["optimizer_state_dict"])
     if scaler is not None and "scaler_state_dict" in checkpoint:
         scaler.load_state_dict(checkpoint["scaler_state_dict"])
+    if source is not None and "stream_state" in checkpoint:
+        source.load_state_dict(checkpoint["stream_state"])
     epoch = checkpoint["epoch"]
     loss = checkpoint["loss"]
     if plot:

@@ -79,6 +79,9 @@ SIGNATURES = {
     "sqr_loss_grad_scale": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p]),
     "sqr_implicit_render": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
     "sqr_scan_render": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sqr_sq_sample": (c_int, [c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, c_int, c_void_p,
+                              c_void_p, c_void_p]),
+    "sqr_sq_stream_advance": (c_int, [c_void_p, ctypes.c_uint64, c_void_p]),
     "sqr_explicit_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "sqr_explicit_loss_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                           c_void_p, c_size_t, c_void_p]),

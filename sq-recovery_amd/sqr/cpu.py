@@ -260,3 +260,56 @@ def scan_render(params, size=256, levels=255, dtype=torch.float64, return_fmin=F
         sub = rays.take(idx)
         fmin[idx] = torch.exp2(sub.e1 * sub.minimise(w0[idx], w1[idx], n1)[1])
     return depth, fmin.reshape(rays.B, rays.S, rays.S)
+
+
+# ---------------------------------------------------------------- the online label sampler (sqr_sq_sample)
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 over arrays: counter = four uint32-valued arrays of one shape, key = two Python ints;
+    returns the four output words as uint64 arrays holding 32-bit values."""
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & _U32 for c in counter)
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2  # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ np.uint64(k0), p1 & _U32, (p0 >> _S32) ^ c3 ^ np.uint64(k1), p0 & _U32
+        k0, k1 = (k0 + _PHILOX_W0) & 0xFFFFFFFF, (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def sq_sample_raw(position, n, seed=0, substream=0):
+    """The [n, 12] uint32 words of samples position .. position + n - 1 (modulo 2^64) of `substream` under
+    `seed`: three Philox calls per sample, counter (i_lo, i_hi, call, substream), key (seed_lo, seed_hi)."""
+    seed, position = int(seed) & (2 ** 64 - 1), int(position) & (2 ** 64 - 1)
+    i = np.uint64(position) + np.arange(n, dtype=np.uint64)  # wraps modulo 2^64
+    lo, hi = i & _U32, i >> _S32
+    sub = np.full(n, int(substream) & 0xFFFFFFFF, dtype=np.uint64)
+    words = []
+    for call in range(3):
+        words.extend(philox4x32_10((lo, hi, np.full(n, call, dtype=np.uint64), sub), (seed, seed >> 32)))
+    return np.stack(words, 1).astype(np.uint32)
+
+
+def sq_uniforms(raw):
+    """u_j = (w_j >> 8) 2^-24 of the first eleven words: [n, 11] float64, each exactly a float32."""
+    return (np.asarray(raw)[:, :11] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+
+
+def sq_labels(u):
+    """[n, 12] float32 labels [a(3), e(2), t(3), q(4)] of [n, 11] uniforms (float64 arithmetic, one rounding):
+    the distribution of classes.sample_sq_params."""
+    u = np.asarray(u, dtype=np.float64)
+    r1, r2 = np.sqrt(1.0 - u[:, 8]), np.sqrt(u[:, 8])
+    a1, a2 = 2.0 * np.pi * u[:, 9], 2.0 * np.pi * u[:, 10]
+    q = np.stack([r1 * np.sin(a1), r1 * np.cos(a1), r2 * np.sin(a2), r2 * np.cos(a2)], 1)
+    return np.concatenate([(25.0 + 50.0 * u[:, 0:3]) / 255.0, 0.1 + 0.9 * u[:, 3:5],
+                           (88.0 + 80.0 * u[:, 5:8]) / 255.0, q], 1).astype(np.float32)
+
+
+def sq_sample(position, n, seed=0, substream=0):
+    """Host restatement of sqr_sq_sample: the [n, 12] float32 labels of samples position .. position + n - 1."""
+    return sq_labels(sq_uniforms(sq_sample_raw(position, n, seed, substream)))

@@ -20,6 +20,10 @@ Adam (and the fp16 loss scaler) — is captured once and replayed per batch:
 
 The first batch runs eagerly (it initialises the optimizer state, the packed weights and the
 gradient buffers outside the capture); every batch is trained exactly once, as in the reference.
+
+With a ``source`` (sqr.data.OnlineSource.next: a capturable callable that makes the batch on the device
+from a position kept in device memory) the batch is drawn inside the step: ``step()`` takes no batch,
+nothing is copied into static buffers, and each replay trains on the source's next batch.
 """
 import torch
 
@@ -29,10 +33,13 @@ RING = 64
 class CapturedStep:
     """``body(x, labels) -> loss`` (0-d tensor; performs backward, all-reduce and the optimizer
     step, gradients cleared to None before it) run per batch, captured after its first call.
-    ``check`` (optional): a callable returning the tensor whose NaN status is reported per step."""
+    ``check`` (optional): a callable returning the tensor whose NaN status is reported per step.
+    ``source`` (optional): a capturable callable returning the next (x, labels) made on the device; the
+    step then draws its own batch (``step()`` without arguments) and the draw is part of the graph."""
 
-    def __init__(self, body, optimizer, device, check=None, zero_grad=None, graph=True):
+    def __init__(self, body, optimizer, device, check=None, zero_grad=None, graph=True, source=None):
         self.body = body
+        self.source = source
         self.use_graph = graph
         self.opt = optimizer
         self.device = torch.device(device)
@@ -57,6 +64,8 @@ class CapturedStep:
 
     def _eager(self, x, y):
         self.zero_grad()
+        if self.source is not None:
+            x, y = self.source()
         return self._pair(self.body(x, y))
 
     def _capture(self, x, y, key):
@@ -66,29 +75,37 @@ class CapturedStep:
             # all-reduces on the communicator — drain, then destroy it, as sqr.dist.finish does
             torch.cuda.synchronize(self.device)
             old.reset()
-        self.static_x = x.detach().clone()
-        self.static_y = y.detach().clone()
+        if self.source is None:
+            self.static_x = x.detach().clone()
+            self.static_y = y.detach().clone()
         self.zero_grad()
         g = torch.cuda.CUDAGraph()
         # thread_local: a DataLoader pin-memory thread allocating during the capture is not an error
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self.out = self._pair(self.body(self.static_x, self.static_y))
+            if self.source is not None:  # the draw is captured: the position it reads lives in device memory
+                self.out = self._pair(self.body(*self.source()))
+            else:
+                self.out = self._pair(self.body(self.static_x, self.static_y))
         self.graph, self.key = g, key
         self.captures += 1
 
-    def step(self, x, y):
-        """Train on one batch (asynchronous); its (loss, nan) come out of a later drain()."""
+    def step(self, x=None, y=None):
+        """Train on one batch (asynchronous); its (loss, nan) come out of a later drain().  With a source
+        the step draws the batch itself and takes no arguments."""
         slot = self.launched % RING
         if self.launched - self.read >= RING:
             raise RuntimeError("CapturedStep: drain() the ring before issuing %d more steps" % RING)
-        shape = (tuple(x.shape), tuple(y.shape), x.dtype)
+        if (self.source is None) == (x is None):
+            raise ValueError("CapturedStep.step: pass a batch, or build the step with a source (not both)")
+        shape = (tuple(x.shape), tuple(y.shape), x.dtype) if self.source is None else ("source",)
         key = shape + (self._lrs(),)
         if self.launched == 0 or self.device.type != "cuda" or not self.use_graph:
             self.full = shape  # the eager warm-up batch sets the captured batch shape
             pair = self._eager(x, y)
         elif key == self.key:
-            self.static_x.copy_(x, non_blocking=True)
-            self.static_y.copy_(y, non_blocking=True)
+            if self.source is None:
+                self.static_x.copy_(x, non_blocking=True)
+                self.static_y.copy_(y, non_blocking=True)
             self.graph.replay()
             pair = self.out
         elif shape == self.full:  # first full-size batch after the warm-up, or new learning rates

@@ -23,6 +23,11 @@ MI355X-specific:
   * --synthetic N trains on N rendered SQ images (no dataset files needed; --synthetic-render scanner: the
     scanner's hard depth maps, sqr_scan_render, instead of the soft ImplicitLoss render); otherwise the
     reference's H5Dataset(dataset_location, parse_csv(labels), 0.9) is used (needs h5py);
+  * --online STEPS trains on an endless stream of fresh samples instead: each step draws its batch's labels on
+    the device (sqr_sq_sample, a counter-based generator: sample i is the same image whatever the batch size,
+    the number of GPUs or a resumed run) and renders them there (sqr.data.OnlineSource), inside the step graph;
+    validation reads the fixed samples [0, --online-val) of substream 1; the checkpoint carries the stream's
+    position ('stream_state') and --continue-training resumes there;
   * on CUDA the whole training step (forward, loss, backward, all-reduce, Adam / loss scaler) is
     captured in one HIP graph and replayed per batch (sqr.step.CapturedStep: static batch buffers,
     loss and the NaN check of encoder.fc[0].weight.grad read back one step behind, so the host
@@ -46,7 +51,7 @@ from classes import (ExplicitLoss, H5Dataset, ImplicitLoss, IoUAccuracy, LeastSq
 from helpers import load_model, parse_csv, save_compare_images, save_model  # noqa: E402
 from models import ResNetSQ  # noqa: E402
 from sqr import amp, dist  # noqa: E402
-from sqr.data import DevicePrefetcher  # noqa: E402
+from sqr.data import DevicePrefetcher, OnlineSource  # noqa: E402
 from sqr.optim import Adam  # noqa: E402
 from sqr.step import CapturedStep  # noqa: E402
 from sqr.tail import cat_heads  # noqa: E402
@@ -57,8 +62,15 @@ def parse_args(argv=None):
     ap.add_argument("--dataset-location", default="../data/data/")
     ap.add_argument("--labels", default="../data/annotations/data_labels.csv")
     ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images instead of the h5 set")
-    ap.add_argument("--synthetic-render", default="soft", choices=("soft", "scanner"),
-                    help="--synthetic images: the soft ImplicitLoss render, or the scanner's hard depth maps")
+    ap.add_argument("--synthetic-render", default=None, choices=("soft", "scanner"),
+                    help="--synthetic / --online images: the soft ImplicitLoss render, or the scanner's hard depth "
+                         "maps (default: soft for --synthetic, scanner for --online)")
+    ap.add_argument("--online", type=int, default=0,
+                    help="train on STEPS fresh batches per epoch and rank, drawn and rendered on the device inside "
+                         "the step (no dataset; exclusive with --synthetic)")
+    ap.add_argument("--online-val", type=int, default=1024,
+                    help="--online: validate on samples [0, N) of substream 1 (whole batches over all ranks)")
+    ap.add_argument("--seed", type=int, default=0, help="--online: seed of the sample streams")
     ap.add_argument("--model-location", default="trained_models/model_full.pt")
     ap.add_argument("--epochs", type=int, default=20000)
     ap.add_argument("--batch-size", type=int, default=32, help="per-GPU batch")
@@ -85,7 +97,14 @@ def parse_args(argv=None):
     ap.add_argument("--dp-rehearsal", action="store_true",
                     help="one CUDA rank: run the N>1 data path (flat gradient buffer, bucketed all-reduce on "
                          "libsqr's RCCL communicator, captured in the step graph) on a world-1 communicator")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.online and args.synthetic:
+        ap.error("--online and --synthetic are exclusive")
+    if args.online < 0 or (args.online and args.online_val < 1):
+        ap.error("--online needs STEPS >= 1 and --online-val >= 1")
+    if args.synthetic_render is None:
+        args.synthetic_render = "scanner" if args.online else "soft"
+    return args
 
 
 def _batches(dataset, rank, world, batch_size, device=torch.device("cpu")):
@@ -113,7 +132,16 @@ def main(argv=None):
     if main_rank:
         print("Using device: %s (world size %d)" % (device, world))
 
-    if args.synthetic:
+    source = val_source = dataset = None
+    if args.online:
+        # the ranks together consume one contiguous stream; validation: substream 1 from position 0, whole
+        # batches of at most --batch-size over all ranks
+        kw = dict(seed=args.seed, rank=rank, world=world, render=args.synthetic_render)
+        source = OnlineSource(args.batch_size, device, substream=0, **kw)
+        val_batch = min(args.batch_size, max(1, args.online_val // world))
+        val_steps = max(1, args.online_val // (world * val_batch))
+        val_source = OnlineSource(val_batch, device, substream=1, **kw)
+    elif args.synthetic:
         # every rank renders the same set and trains on its own shard
         dataset = SyntheticDataset(args.synthetic, device, train_split=0.9, seed=0, render=args.synthetic_render)
     else:
@@ -131,7 +159,8 @@ def main(argv=None):
     if args.continue_training:
         if main_rank:
             print("Continuing with training...")
-        starting_epoch, net, optimizer, _ = load_model(args.model_location, net, optimizer, scaler=scaler)
+        starting_epoch, net, optimizer, _ = load_model(args.model_location, net, optimizer, scaler=scaler,
+                                                       source=source)
     # N > 1: bucketed gradient all-reduce overlapped with backward (the same machinery bench.py
     # captures in its step graph); the model itself stays unwrapped (checkpoints keep plain keys)
     if args.dp_rehearsal and world == 1 and use_cuda:
@@ -175,15 +204,32 @@ def main(argv=None):
     # the reference's per-step NaN check (train.py:115) on encoder.fc[0].weight.grad
     # (a gloo process group on CUDA — several ranks on one GPU — all-reduces through the host: eager)
     stepper = CapturedStep(train_body, optimizer, device, check=lambda: net.encoder.fc[0].weight.grad,
-                           graph=bool(args.graph) and dist.capturable())
+                           graph=bool(args.graph) and dist.capturable(),
+                           source=source.next if source is not None else None)
+
+    def epoch_batches(mode):
+        """(x, labels) of the epoch's split; --online training steps draw their own batch: (None, None)."""
+        if source is None:
+            dataset.set_mode(mode)
+            yield from _batches(dataset, rank, world, args.batch_size, device)
+        elif mode == 0:
+            for _ in range(args.online):
+                yield None, None
+        else:
+            val_source.seek(0)  # the same set every epoch, re-rendered
+            for _ in range(val_steps):
+                yield val_source.next()
 
     best_val_loss = None
     mean_losses, mean_val_losses, mean_val_accs = [], [], []
     for epoch in range(starting_epoch, args.epochs):
         losses, val_losses, val_accuracies = [], [], []
         net.train()
-        dataset.set_mode(0)
-        n_items = len(dataset)
+        if source is None:
+            dataset.set_mode(0)
+            n_items = len(dataset)
+        else:
+            n_items = args.online * args.batch_size * world
         sizes = []
 
         def report(results):
@@ -201,12 +247,16 @@ def main(argv=None):
 
         dist.barrier()
         t0 = time.perf_counter()
-        for batch_idx, (x, true_labels) in enumerate(_batches(dataset, rank, world, args.batch_size, device)):
+        for batch_idx, (x, true_labels) in enumerate(epoch_batches(0)):
             if args.max_steps and batch_idx >= args.max_steps:
                 break
-            x, true_labels = x.to(device, non_blocking=True), true_labels.to(device, non_blocking=True)
-            sizes.append(len(x))
-            stepper.step(x, true_labels)
+            if source is None:
+                x, true_labels = x.to(device, non_blocking=True), true_labels.to(device, non_blocking=True)
+                sizes.append(len(x))
+                stepper.step(x, true_labels)
+            else:
+                sizes.append(args.batch_size)
+                stepper.step()
             # log one step behind: the previous step has finished by the time this one is queued
             report(stepper.drain(stepper.launched - 1 if stepper.graph is not None else None))
         report(stepper.drain())
@@ -225,9 +275,8 @@ def main(argv=None):
             print("Train Epoch: {} [(100%)]\tLoss: {:.6f}".format(epoch, train_mean))
 
         net.eval()
-        dataset.set_mode(1)
         with torch.no_grad():
-            for batch_idx, (x, true_labels) in enumerate(_batches(dataset, rank, world, args.batch_size, device)):
+            for batch_idx, (x, true_labels) in enumerate(epoch_batches(1)):
                 if args.max_steps and batch_idx >= args.max_steps:
                     break
                 x, true_labels = x.to(device), true_labels.to(device)
@@ -251,7 +300,7 @@ def main(argv=None):
                 os.makedirs(os.path.dirname(args.model_location) or ".", exist_ok=True)
                 save_model(args.model_location, epoch, model, optimizer,
                            {"loss": mean_losses, "val_loss": mean_val_losses, "val_acc": mean_val_accs},
-                           scaler=scaler)
+                           scaler=scaler, source=source)
             print("-" * 72)
             print("Validation Epoch: {}\tLoss: {:,.6f}\tAccuracy: {:,.6f}".format(epoch, val_loss_mean,
                                                                                  val_accuracy_mean))

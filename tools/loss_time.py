@@ -31,7 +31,14 @@ reports the IoU of the three-start and of the six-start scored winners.
 
 times the scanner-style depth render (sqr_scan_render) at B = 256, S = 256, eagerly and inside a replayed
 graph, next to implicit_render at the same B and S (the render it stands beside in SyntheticDataset; the two
-produce different images) and to the float64 host renderer on 16 threads over 16 of the images."""
+produce different images) and to the float64 host renderer on 16 threads over 16 of the images.
+
+    python tools/loss_time.py online
+
+times sqr.data.OnlineSource.next() (sampler, advance, scanner render) at B = 64, size 256, eagerly and inside
+a replayed graph, next to scan_render alone on the same labels and to the sampler + advance alone, in the
+same process; the difference of the first two is the cost of drawing the labels on the device.  It measures
+everything twice and prints one JSON line per pass."""
 import json
 import os
 import sys
@@ -225,9 +232,40 @@ def scan(dev, S=256, B=256, host_images=16):
     return res
 
 
+def online(dev, S=256, B=64):
+    from sqr import _lib, data
+    src = data.OnlineSource(B, dev, size=S)
+    img, lab = src.next()
+    labels = lab.clone()  # scan_render alone: the same labels every call, into the source's image buffer
+
+    def render_only():
+        _lib.check(_lib.lib().sqr_scan_render(_lib.ptr(labels), B, S, 255, _lib.ptr(src.images),
+                                              _lib.stream_ptr(dev)), "sqr_scan_render")
+
+    def draw_only():
+        data.sq_sample(src._pos, src.seed, src.substream, 0, B, src.labels)
+        data.stream_advance(src._pos, B)
+
+    res = {"shape": "S%d_B%d" % (S, B), "foreground_share": round(float((img > 0).float().mean()), 4),
+           "next_eager_ms": round(_eager_ms(src.next, reps=400), 4),
+           "scan_render_eager_ms": round(_eager_ms(render_only, reps=400), 4),
+           "sample_advance_eager_ms": round(_eager_ms(draw_only, reps=400), 4),
+           "next_in_graph_us": round(_graph_us(src.next, reps=400), 2),
+           "scan_render_in_graph_us": round(_graph_us(render_only, reps=400), 2),
+           "sample_advance_in_graph_us": round(_graph_us(draw_only, reps=400), 2)}
+    res["next_minus_render_in_graph_us"] = round(res["next_in_graph_us"] - res["scan_render_in_graph_us"], 2)
+    res["position_after"] = src.position()
+    return res
+
+
 def main():
     dev = torch.device("cuda", 0)
     out = {"env": {k: v for k, v in os.environ.items() if k.startswith("SQR_")}}
+    if sys.argv[1:] == ["online"]:
+        for _ in range(2):  # every figure twice in one process: one JSON line per pass
+            out["online"] = online(dev)
+            print(json.dumps(out))
+        return
     if sys.argv[1:] == ["scan"]:
         out["scan"] = scan(dev)
         print(json.dumps(out))
