@@ -268,16 +268,21 @@ int sqr_lsq_starts(const float* target, int B, int H, int W, int R, float e0, fl
 int sqr_lsq_select(int B, int K, const float* params, const double* energy, float* out_params, double* out_energy,
                    int* out_index, void* stream);
 
-/* Workspace (bytes, device) needed by sqr_lsq_recover for B samples at render size R. */
+/* Workspace (bytes, device) needed by sqr_lsq_recover for B samples at render size R:
+ * B 15 8 (the moments) + max(sqr_lsq_starts_workspace_bytes(B, R), sqr_lsq_lm_refine_workspace_bytes(3 B, R))
+ * + B 36 4 (the starts) + B 4 (the counts): the three starts are refined side by side. */
 size_t sqr_lsq_recover_workspace_bytes(int B, int R);
 
-/* Recovery of B superquadrics from their depth images alone: sqr_lsq_starts, then sqr_lsq_lm_refine from
- * each of the three starts (one after the other on `stream`, in one workspace region), then sqr_lsq_select
- * on the three final energies.  No host wait, no allocation: capturable.
+/* Recovery of B superquadrics from their depth images alone: sqr_lsq_starts, then one
+ * sqr_lsq_lm_refine_multi over the 3 B samples (every start of every image in one chain of launches on
+ * `stream`; bitwise what three sqr_lsq_lm_refine calls on the starts return), then sqr_lsq_select on the
+ * three final energies: sqr_lsq_recover_multi's chain without the free-space evaluation.  No host wait, no
+ * allocation: capturable.
  *   params_out [B,12] f32, energy_out [B] f64, index_out [B] i32 : the winner, its energy, its start
  *   all_params [3,B,12] f32, all_before [3,B] f64, all_after [3,B] f64, all_accepted [3,B] i32 : every
  *   start's refined parameters, energy at the projected start, final energy and accepted steps.
- * Arguments as sqr_lsq_starts and sqr_lsq_lm_refine; SQR_E_INVALID_ARG (nothing launched) as there. */
+ * 3 B <= 65535 (the batched launches' grid); the other arguments as sqr_lsq_starts and sqr_lsq_lm_refine;
+ * SQR_E_INVALID_ARG (nothing launched) as there. */
 int sqr_lsq_recover(const float* target, int B, int H, int W, int R, int iters, float e0, double lambda0, double up,
                     double down, float* params_out, double* energy_out, int* index_out, float* all_params,
                     double* all_before, double* all_after, int* all_accepted, void* workspace,

@@ -10,9 +10,9 @@ visible points — not a higher IoU against a label: the depth image shows one s
 
 Everything runs on the device (Adam: sqr_least_squares_fwd_bwd per step plus a handful of elementwise
 launches on the [B,12] tensor; LM: sqr_lsq_lm_refine, one chain of normal-equations and step kernels;
-recover: sqr_lsq_recover, the starts' four launches, three such chains and a selection, or
-sqr_lsq_recover_multi, every start in one such chain, a free-space evaluation and a scored selection);
-nothing is read back inside the loop.
+recover: the starts' four launches, one such chain over every start of every image and a selection,
+sqr_lsq_recover on the lowest energy of three starts, sqr_lsq_recover_multi on a score with a free-space
+evaluation, from three or six starts and the caller's); nothing is read back inside the loop.
 """
 import torch
 
@@ -50,8 +50,10 @@ def recover(images, iters=30, render_size=32, e0=1.0, lambda0=1e-3, up=10.0, dow
     energy 0.  Every sample is recovered on its own; no host wait, so the call can be captured in a HIP
     graph.
 
-    The defaults (starts="classic", free_space=0, no extra_starts) are that call, sqr_lsq_recover.  Anything
-    else goes through sqr_lsq_recover_multi, one chain over all K B samples:
+    The defaults (starts="classic", free_space=0, no extra_starts) are that call, sqr_lsq_recover: the three
+    starts of every image refined in one chain over all 3 B samples (so 3 B <= 65535) and selected by energy.
+    Anything else goes through sqr_lsq_recover_multi, the same chain over all K B samples with a free-space
+    evaluation behind it:
       starts="depth"   six starts, K = 6: the three above and three whose extent along the frame axis nearest
                        the viewing direction is stretched by `depth` times itself away from the viewer (the
                        image shows the front half of the body only: lsq_starts6)

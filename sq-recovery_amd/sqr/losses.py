@@ -16,6 +16,11 @@ def _require_cuda(*ts):
             raise ValueError("sqr GPU loss called with a CPU tensor (device %s)" % t.device)
 
 
+def _workspace(nbytes, device):
+    """The device bytes a call's *_workspace_bytes asks for (never an empty tensor: its pointer would be null)."""
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device)
+
+
 def _scale_grad(grad, gout, dtype):
     """grad * gout (gout: the scalar loss's upstream gradient, any float dtype) in one launch."""
     g = gout.to(torch.float64) if gout.dtype != torch.float64 else gout
@@ -60,7 +65,7 @@ class ImplicitLossFn(torch.autograd.Function):
         grad = torch.empty(B, 12, dtype=torch.float32, device=p.device) if need_grad else None
         L = lib()
         wsb = L.sqr_implicit_loss_workspace_bytes(B, R)
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+        ws = _workspace(wsb, p.device)
         check(L.sqr_implicit_loss_fwd_bwd_mean(ptr(p), ptr(t), B, H, W, int(R), float(tau), float(sharpness),
                                                int(need_grad), ptr(loss_ps), ptr(loss), ptr(grad), ptr(ws), wsb,
                                                stream_ptr(p.device)), "sqr_implicit_loss_fwd_bwd_mean")
@@ -95,7 +100,7 @@ class ExplicitLossFn(torch.autograd.Function):
         grad = torch.empty(B, 12, dtype=torch.float32, device=pp.device) if need_grad else None
         L = lib()
         wsb = L.sqr_explicit_loss_workspace_bytes(B, R)
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=pp.device)
+        ws = _workspace(wsb, pp.device)
         check(L.sqr_explicit_loss_fwd_bwd_mean(ptr(pt), ptr(pp), B, int(R), int(need_grad), ptr(loss_ps), ptr(loss),
                                                ptr(grad), ptr(ws), wsb, stream_ptr(pp.device)),
               "sqr_explicit_loss_fwd_bwd_mean")
@@ -127,7 +132,7 @@ class LeastSquaresFn(torch.autograd.Function):
         grad = torch.empty(B, 12, dtype=torch.float32, device=p.device) if need_grad else None
         L = lib()
         wsb = L.sqr_least_squares_workspace_bytes(B, R)
-        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+        ws = _workspace(wsb, p.device)
         check(L.sqr_least_squares_fwd_bwd_mean(ptr(p), ptr(t), B, H, W, int(R), int(need_grad), ptr(loss_ps),
                                                ptr(loss), ptr(grad), ptr(ws), wsb, stream_ptr(p.device)),
               "sqr_least_squares_fwd_bwd_mean")
@@ -175,30 +180,37 @@ def least_squares_normal_eq(target, params, R):
     E = torch.empty(B, dtype=torch.float64, device=p.device)
     L = lib()
     wsb = L.sqr_least_squares_normal_eq_workspace_bytes(B, int(R))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+    ws = _workspace(wsb, p.device)
     check(L.sqr_least_squares_normal_eq(ptr(p), ptr(t), B, H, W, int(R), ptr(JtJ), ptr(Jtr), ptr(E), ptr(ws), wsb,
                                         stream_ptr(p.device)), "sqr_least_squares_normal_eq")
     return JtJ, Jtr, E
 
 
+def _lm_refine(t, p, R, iters, lambda0, up, down):
+    """sqr_lsq_lm_refine_multi on checked tensors: t [B,H,W] and p [K,B,12], contiguous float32 on one device."""
+    (K, B, _), (H, W), dev = p.shape, t.shape[1:], p.device
+    out = torch.empty(K, B, 12, dtype=torch.float32, device=dev)
+    before = torch.empty(K, B, dtype=torch.float64, device=dev)
+    after = torch.empty(K, B, dtype=torch.float64, device=dev)
+    accepted = torch.empty(K, B, dtype=torch.int32, device=dev)
+    L = lib()
+    wsb = L.sqr_lsq_lm_refine_workspace_bytes(K * B, int(R))
+    ws = _workspace(wsb, dev)
+    check(L.sqr_lsq_lm_refine_multi(ptr(p), ptr(t), K, B, H, W, int(R), int(iters), float(lambda0), float(up),
+                                    float(down), ptr(out), ptr(before), ptr(after), ptr(accepted), ptr(ws), wsb,
+                                    stream_ptr(dev)), "sqr_lsq_lm_refine_multi")
+    return out, before, after, accepted
+
+
 def lm_refine(target, params, R, iters, lambda0, up, down):
-    """sqr_lsq_lm_refine -> (params [B,12] f32, energy_before [B] f64, energy_after [B] f64, accepted [B]
-    i32).  One chain of launches on the current stream; no host wait."""
+    """sqr_lsq_lm_refine_multi with K = 1 (what the C entry sqr_lsq_lm_refine is too; an error names the multi
+    entry) -> (params [B,12] f32, energy_before [B] f64, energy_after [B] f64, accepted [B] i32).  One chain of
+    launches on the current stream; no host wait."""
     _require_cuda(target, params)
     tgt, B, H, W = _image_target(target, params)
     p = params.detach().to(torch.float32).contiguous()
     t = tgt.detach().to(torch.float32).contiguous()
-    out = torch.empty(B, 12, dtype=torch.float32, device=p.device)
-    before = torch.empty(B, dtype=torch.float64, device=p.device)
-    after = torch.empty(B, dtype=torch.float64, device=p.device)
-    accepted = torch.empty(B, dtype=torch.int32, device=p.device)
-    L = lib()
-    wsb = L.sqr_lsq_lm_refine_workspace_bytes(B, int(R))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
-    check(L.sqr_lsq_lm_refine(ptr(p), ptr(t), B, H, W, int(R), int(iters), float(lambda0), float(up), float(down),
-                              ptr(out), ptr(before), ptr(after), ptr(accepted), ptr(ws), wsb, stream_ptr(p.device)),
-          "sqr_lsq_lm_refine")
-    return out, before, after, accepted
+    return tuple(x[0] for x in _lm_refine(t, p[None], R, iters, lambda0, up, down))
 
 
 def _image_only(target):
@@ -216,26 +228,38 @@ def _image_only(target):
     return t, int(t.shape[0]), int(t.shape[1]), int(t.shape[2])
 
 
+def _moments_info(B, dev):
+    """The empty outputs of the starts' moments: count [B] i32, centroid [B,3], eigenvalues [B,3], frame [B,3,3]."""
+    f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)  # noqa: E731
+    return {"count": torch.empty(B, dtype=torch.int32, device=dev), "centroid": f64(B, 3), "eigenvalues": f64(B, 3),
+            "frame": f64(B, 3, 3)}
+
+
+def _starts(target, R, e0, depth):
+    """sqr_lsq_starts (depth None: three starts) or sqr_lsq_starts6 (six) -> (starts [3 or 6,B,12] f32, info)."""
+    t, B, H, W = _image_only(target)
+    dev = t.device
+    starts = torch.empty(3 if depth is None else 6, B, 12, dtype=torch.float32, device=dev)
+    info = _moments_info(B, dev)
+    L = lib()
+    wsb = L.sqr_lsq_starts_workspace_bytes(B, int(R))
+    ws = _workspace(wsb, dev)
+    outs = (ptr(starts), ptr(info["count"]), ptr(info["centroid"]), ptr(info["eigenvalues"]), ptr(info["frame"]),
+            ptr(ws), wsb, stream_ptr(dev))
+    if depth is None:
+        check(L.sqr_lsq_starts(ptr(t), B, H, W, int(R), float(e0), *outs), "sqr_lsq_starts")
+    else:
+        check(L.sqr_lsq_starts6(ptr(t), B, H, W, int(R), float(e0), float(depth), *outs), "sqr_lsq_starts6")
+    return starts, info
+
+
 def lsq_starts(target, R, e0=1.0):
     """sqr_lsq_starts -> (starts [3,B,12] f32, info): Solina & Bajcsy's three starts of the recovery from the
     points of each image alone.  info: count [B] i32, centroid [B,3], eigenvalues [B,3] (of the points'
     covariance, ascending) and frame [B,3,3] (the eigenvectors its columns, det +1), float64.  Start k has the
     columns (k, k+1, k+2 mod 3) of the frame as its axes, half the points' extents along them as its sizes and
     e = (e0, e0).  Four launches on the current stream; no host wait."""
-    t, B, H, W = _image_only(target)
-    dev = t.device
-    starts = torch.empty(3, B, 12, dtype=torch.float32, device=dev)
-    info = {"count": torch.empty(B, dtype=torch.int32, device=dev),
-            "centroid": torch.empty(B, 3, dtype=torch.float64, device=dev),
-            "eigenvalues": torch.empty(B, 3, dtype=torch.float64, device=dev),
-            "frame": torch.empty(B, 3, 3, dtype=torch.float64, device=dev)}
-    L = lib()
-    wsb = L.sqr_lsq_starts_workspace_bytes(B, int(R))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    check(L.sqr_lsq_starts(ptr(t), B, H, W, int(R), float(e0), ptr(starts), ptr(info["count"]), ptr(info["centroid"]),
-                           ptr(info["eigenvalues"]), ptr(info["frame"]), ptr(ws), wsb, stream_ptr(dev)),
-          "sqr_lsq_starts")
-    return starts, info
+    return _starts(target, R, e0, None)
 
 
 def lsq_select(params, energy):
@@ -271,7 +295,7 @@ def lsq_recover(target, R, iters, e0, lambda0, up, down):
     accepted = torch.empty(3, B, dtype=torch.int32, device=dev)
     L = lib()
     wsb = L.sqr_lsq_recover_workspace_bytes(B, int(R))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(wsb, dev)
     check(L.sqr_lsq_recover(ptr(t), B, H, W, int(R), int(iters), float(e0), float(lambda0), float(up), float(down),
                             ptr(out), ptr(energy), ptr(index), ptr(allp), ptr(before), ptr(after), ptr(accepted),
                             ptr(ws), wsb, stream_ptr(dev)), "sqr_lsq_recover")
@@ -305,7 +329,7 @@ def free_space_energy(images, params, render_size, margin=1.0 / 255.0):
     out = torch.empty(S, dtype=torch.float64, device=p.device)
     L = lib()
     wsb = L.sqr_lsq_free_space_workspace_bytes(S, int(render_size))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=p.device)
+    ws = _workspace(wsb, p.device)
     check(L.sqr_lsq_free_space(ptr(p), ptr(t), S, B, H, W, int(render_size), float(margin), ptr(out), ptr(ws), wsb,
                                stream_ptr(p.device)), "sqr_lsq_free_space")
     return out
@@ -315,40 +339,15 @@ def lm_refine_multi(target, params, R, iters, lambda0, up, down):
     """sqr_lsq_lm_refine_multi: params [K,B,12], target [B,1,H,W] or [B,H,W] -> (params [K,B,12] f32,
     energy_before [K,B] f64, energy_after [K,B] f64, accepted [K,B] i32), bitwise what K lm_refine calls on the
     slices return.  One chain of launches over the K B samples on the current stream; no host wait."""
-    t, B, H, W = _image_only(target)
-    p = _stacked_params(params, B, "params")
-    K, dev = int(p.shape[0]), p.device
-    out = torch.empty(K, B, 12, dtype=torch.float32, device=dev)
-    before = torch.empty(K, B, dtype=torch.float64, device=dev)
-    after = torch.empty(K, B, dtype=torch.float64, device=dev)
-    accepted = torch.empty(K, B, dtype=torch.int32, device=dev)
-    L = lib()
-    wsb = L.sqr_lsq_lm_refine_workspace_bytes(K * B, int(R))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    check(L.sqr_lsq_lm_refine_multi(ptr(p), ptr(t), K, B, H, W, int(R), int(iters), float(lambda0), float(up),
-                                    float(down), ptr(out), ptr(before), ptr(after), ptr(accepted), ptr(ws), wsb,
-                                    stream_ptr(dev)), "sqr_lsq_lm_refine_multi")
-    return out, before, after, accepted
+    t, B, _, _ = _image_only(target)
+    return _lm_refine(t, _stacked_params(params, B, "params"), R, iters, lambda0, up, down)
 
 
 def lsq_starts6(target, R, e0=1.0, depth=1.0):
     """sqr_lsq_starts6 -> (starts [6,B,12] f32, info as lsq_starts): lsq_starts' three starts, bitwise, and
     three more whose extent along the frame axis nearest the viewing direction is stretched by depth times
     itself away from the viewer (a depth image shows the front half only).  depth = 0 repeats starts 0..2."""
-    t, B, H, W = _image_only(target)
-    dev = t.device
-    starts = torch.empty(6, B, 12, dtype=torch.float32, device=dev)
-    info = {"count": torch.empty(B, dtype=torch.int32, device=dev),
-            "centroid": torch.empty(B, 3, dtype=torch.float64, device=dev),
-            "eigenvalues": torch.empty(B, 3, dtype=torch.float64, device=dev),
-            "frame": torch.empty(B, 3, 3, dtype=torch.float64, device=dev)}
-    L = lib()
-    wsb = L.sqr_lsq_starts_workspace_bytes(B, int(R))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    check(L.sqr_lsq_starts6(ptr(t), B, H, W, int(R), float(e0), float(depth), ptr(starts), ptr(info["count"]),
-                            ptr(info["centroid"]), ptr(info["eigenvalues"]), ptr(info["frame"]), ptr(ws), wsb,
-                            stream_ptr(dev)), "sqr_lsq_starts6")
-    return starts, info
+    return _starts(target, R, e0, depth)
 
 
 def lsq_recover_multi(target, R, iters, nstarts, e0, depth, extra, lambda0, up, down, w_fs, margin):
@@ -371,7 +370,7 @@ def lsq_recover_multi(target, R, iters, nstarts, e0, depth, extra, lambda0, up, 
             "accepted": torch.empty(K, B, dtype=torch.int32, device=dev)}
     L = lib()
     wsb = L.sqr_lsq_recover_multi_workspace_bytes(K, B, int(R))
-    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    ws = _workspace(wsb, dev)
     check(L.sqr_lsq_recover_multi(ptr(t), B, H, W, int(R), int(iters), int(nstarts), float(e0), float(depth), ptr(x),
                                   Kx, float(lambda0), float(up), float(down), float(w_fs), float(margin), ptr(out),
                                   ptr(energy), ptr(fs), ptr(index), ptr(info["starts"]), ptr(info["params"]),

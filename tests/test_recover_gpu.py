@@ -367,6 +367,27 @@ def test_recover_batch_independence_repeatability_and_empty_image(run):
     assert np.array_equal(p[1].cpu().numpy(), rr.default_start(1.0))
 
 
+@pytest.mark.parametrize("R,H,W", [(8, 16, 16), (12, 24, 40)])  # a partly filled block; non-square, R no divisor
+def test_recover_is_its_public_parts_composed_by_hand(R, H, W):
+    """sqr_lsq_recover and sqr_lsq_recover_multi run the same chain, so comparing them compares two doors to one
+    room.  Here the recovery is put together from the public parts, lsq_starts, one refine_lm per start on the
+    slices and lsq_select, and fit.recover must return the same bits for every start and for the winner."""
+    from sqr import fit, losses
+    ex, _ = example()
+    img = torch.tensor(_resample(ex, [1, 5, 8], H, W), device=DEV)
+    params, energy, index, info = fit.recover(img, iters=3, render_size=R, return_info=True)
+    starts, _ = losses.lsq_starts(img, R)
+    parts = [fit.refine_lm(img, starts[k], iters=3, render_size=R, return_info=True) for k in range(3)]
+    byhand = [torch.stack([p[i] for p in parts]) for i in range(4)]
+    for got, want, what in zip((info["params"], info["energy_before"], info["energy_after"], info["accepted"]), byhand,
+                               ("params", "energy_before", "energy_after", "accepted")):
+        assert got.dtype == want.dtype and torch.equal(got, want), what
+    assert bool((info["accepted"] > 0).any())  # the three iterations moved something
+    for got, want, what in zip((params, energy, index), losses.lsq_select(byhand[0], byhand[2]),
+                               ("params", "energy", "index")):
+        assert got.dtype == want.dtype and torch.equal(got, want), what
+
+
 def test_recover_captured_in_a_graph_replays_bitwise(run):
     from sqr import fit
     img = run["img"].clone()
@@ -426,7 +447,7 @@ def test_c_abi_writes_inside_its_buffers_only(R, H, W, B):
             assert bool((view != fills[k]).all()) and (k == "count" or bool(torch.isfinite(view).all())), k
     # the whole chain
     wsb = L.sqr_lsq_recover_workspace_bytes(B, R)
-    assert wsb == B * 15 * 8 + max(B * nblk * 16 * 8, L.sqr_lsq_lm_refine_workspace_bytes(B, R)) + B * 36 * 4 + B * 4
+    assert wsb == B * 15 * 8 + max(B * nblk * 16 * 8, L.sqr_lsq_lm_refine_workspace_bytes(3 * B, R)) + B * 36 * 4 + B * 4
     bufs = dict(out=_guarded(B * 12, torch.float32, f), energy=_guarded(B, torch.float64, f),
                 index=_guarded(B, torch.int32, -7), allp=_guarded(3 * B * 12, torch.float32, f),
                 before=_guarded(3 * B, torch.float64, f), after=_guarded(3 * B, torch.float64, f),

@@ -23,9 +23,10 @@ process, and reports the energies, the winning starts and the IoU against the la
     python tools/loss_time.py recover-multi
 
 times the six-start scored recovery (sqr.fit.recover with starts="depth", free_space=1) and free_space_energy
-alone on that batch, eagerly and inside a replayed graph, next to today's three-start recover, to three starts
-through the batched chain and to the batched refinement against three separate ones, in the same process, and
-reports the IoU of the three-start and of the six-start scored winners.
+alone on that batch, eagerly and inside a replayed graph, next to the three-start recover (the same chain over
+3 B samples, selected by energy alone), to the same three starts with the score and to the batched refinement
+against three separate ones, in the same process, and reports the IoU of the three-start and of the six-start
+scored winners.
 
     python tools/loss_time.py scan
 
@@ -141,9 +142,9 @@ def lm(dev, R=64, H=256, B=64):
 
 
 def recover(dev, R=64, H=256, B=64, iters=30):
-    """sqr.fit.recover (the starts, three refinements, the selection) eagerly and inside a graph, next to the
-    starts alone and to one refine_lm with the same `iters` from labels + N(0, 0.02), at the shapes of the lm
-    mode, on scanner-style images of random labels."""
+    """sqr.fit.recover (the starts, one refinement of all 3 B samples, the selection) eagerly and inside a graph,
+    next to the starts alone and to one refine_lm with the same `iters` from labels + N(0, 0.02), at the shapes
+    of the lm mode, on scanner-style images of random labels."""
     from sqr import fit
     p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
     img = losses.scan_render(p, H, 255).unsqueeze(1).contiguous()
@@ -168,9 +169,9 @@ def recover(dev, R=64, H=256, B=64, iters=30):
 
 
 def recover_multi(dev, R=64, H=256, B=64, iters=30):
-    """The recover mode's batch: sqr.fit.recover as it was, three starts through the batched chain, the six-start
-    scored recovery, free_space_energy of the six results, and lm_refine_multi over 3 B samples against three
-    refine_lm calls of B."""
+    """The recover mode's batch: sqr.fit.recover (three starts, selected by energy), the same three starts with the
+    score, the six-start scored recovery, free_space_energy of the six results, and lm_refine_multi over 3 B
+    samples against three refine_lm calls of B."""
     from sqr import fit
     p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
     img = losses.scan_render(p, H, 255).unsqueeze(1).contiguous()
