@@ -33,6 +33,9 @@
  *   sqr_lsq_starts6, sqr_lsq_lm_refine_multi, sqr_lsq_free_space, sqr_lsq_recover_multi
  *                              no counterpart: three more, depth-aware starts, all starts refined as one batch,
  *                              and the winner chosen by point energy plus a free-space energy over every ray
+ *   sqr_pts_normal_eq, sqr_pts_lm_refine, sqr_pts_starts, sqr_pts_recover
+ *                              the same stack on point lists [B,P,3] (LeastSquares.energy_function's own input,
+ *                              classes.py:318-356) instead of depth images
  *   sqr_iou_counts             torch/classes.py:374-447  IoUAccuracy (ins_outs :394-426, __call__ :428-447)
  *   sqr_conv2d_fwd / _bwd_data / _bwd_weight
  *                              torch.nn.Conv2d as used by torchvision resnet18 inside ResNetSQ
@@ -350,6 +353,67 @@ int sqr_lsq_recover_multi(const float* target, int B, int H, int W, int R, int i
                           float margin, float* params_out, double* energy_out, double* energy_fs_out, int* index_out,
                           float* all_starts, float* all_params, double* all_before, double* all_after, double* all_fs,
                           double* all_score, int* all_accepted, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- The fitting stack on point lists (sqr_pts_*): the same kernels with a second point source.
+ * A point list is points [B,P,3] f32 (x, y, z per slot) and count [B] i32 (nullable: every cloud has P slots).
+ * Slot i of cloud b counts iff i < count[b] (count clamped into [0, P]) and all three coordinates are finite; a
+ * slot that does not count adds a zero row / a zero moment term and is ignored by min / max, exactly as a pixel
+ * that is not > 0 is in the image calls.  Coordinates are not restricted to [0,1] and z <= 0 is an ordinary
+ * point (the parameter clamps still assume a body inside the unit cube: scale the cloud first if it is not).
+ * Slots map to threads as resized pixels do: slot i is thread i mod 256 of block i / 256, ceil(P / 256) blocks,
+ * waves and blocks summed in order.  So for the list that is an image's R^2 slots in pixel order (P = R^2,
+ * x = c / R and y = 1 - r / R formed in fp32, z the nearest-resized value, every slot with z <= 0 or NaN set to
+ * NaN) each call below returns bitwise what its image counterpart returns; and a cloud's results do not depend
+ * on P beyond its count (trailing slots add exact zeros), nor on the rest of the batch.
+ * 1 <= P <= 2^20 (the slots of R = 1024).  Padding a short cloud costs 12 bytes per empty slot; a ragged
+ * (offsets) layout is not offered.  Not offered either: the depth-aware starts (sqr_lsq_starts6) and the
+ * free-space energy (sqr_lsq_free_space), which need a viewpoint that a list does not have.
+ * Every argument is checked before the first HIP call: SQR_E_INVALID_ARG (also for a short workspace) launches
+ * nothing. */
+
+/* Workspace (bytes, device) needed by sqr_pts_normal_eq for S samples on lists of P slots. */
+size_t sqr_pts_normal_eq_workspace_bytes(int S, int P);
+
+/* sqr_least_squares_normal_eq on point lists: params [S,12], sample s reads cloud s mod B (S a multiple of B:
+ * a [K,B] stack), JtJ [S,12,12], Jtr [S,12], energy [S] f64.  A cloud without counting slots gives zeros.
+ * 1 <= B <= S <= 65535. */
+int sqr_pts_normal_eq(const float* params, const float* points, const int* count, int S, int B, int P, double* JtJ,
+                      double* Jtr, double* energy, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_pts_lm_refine for S = K B samples on lists of P slots. */
+size_t sqr_pts_lm_refine_workspace_bytes(int S, int P);
+
+/* sqr_lsq_lm_refine_multi on point lists: params_in [K,B,12], sample k B + b on cloud b; the same chain
+ * (sqr_lsq_lm_step unchanged) and the same outputs.  K,B >= 1, K B <= 65535; iters, lambda0, up, down as
+ * sqr_lsq_lm_refine. */
+int sqr_pts_lm_refine(const float* params_in, const float* points, const int* count, int K, int B, int P, int iters,
+                      double lambda0, double up, double down, float* params_out, double* energy_before,
+                      double* energy_after, int* accepted, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_pts_starts for B lists of P slots. */
+size_t sqr_pts_starts_workspace_bytes(int B, int P);
+
+/* sqr_lsq_starts on point lists: starts [3,B,12] f32, count_out [B] i32 (the slots that count), centroid,
+ * eigenvalues, frame as there; the workspace's debugging layout too, with ceil(P / 256) blocks.
+ * 1 <= B <= 65535, 0.1 <= e0 <= 1. */
+int sqr_pts_starts(const float* points, const int* count, int B, int P, float e0, float* starts, int* count_out,
+                   double* centroid, double* eigenvalues, double* frame, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+/* Workspace (bytes, device) needed by sqr_pts_recover for K = 3 + Kx starts of B lists of P slots. */
+size_t sqr_pts_recover_workspace_bytes(int K, int B, int P);
+
+/* The recovery of B superquadrics from their point lists in one chain: sqr_pts_starts' three starts, the
+ * caller's `extra` starts [Kx,B,12] behind them (nullable with Kx = 0), one sqr_pts_lm_refine over the K B
+ * samples, K = 3 + Kx, and sqr_lsq_select on the final energies.  No host wait, no allocation: capturable.
+ *   params_out [B,12] f32, energy_out [B] f64, index_out [B] i32 : the winner, its energy, its start
+ *   all_starts [K,B,12] f32, all_params [K,B,12] f32, all_before / all_after [K,B] f64, all_accepted [K,B] i32
+ * A cloud without counting slots returns the default start with energy 0.  K B <= 65535; the other arguments
+ * as sqr_pts_starts and sqr_pts_lm_refine. */
+int sqr_pts_recover(const float* points, const int* count, int B, int P, int iters, float e0, const float* extra,
+                    int Kx, double lambda0, double up, double down, float* params_out, double* energy_out,
+                    int* index_out, float* all_starts, float* all_params, double* all_before, double* all_after,
+                    int* all_accepted, void* workspace, size_t workspace_bytes, void* stream);
 
 /* IoUAccuracy(R): per-sample voxel counts [B,2] int64 = (|in_true & in_pred|, |in_true | in_pred|),
  * computed in float64 like the reference. */

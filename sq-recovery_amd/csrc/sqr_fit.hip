@@ -1,9 +1,12 @@
 // The classical fitting stack for gfx950 on the LeastSquares energy (classes.py:318-371): its normal equations on
 // f64 MFMA, the Levenberg-Marquardt loop, the classical recovery's starts and selection around it
 // (lsq_moments_kernel .. lsq_select_kernel), the free-space energy over every pixel's ray that the scored
-// selection uses (free_space_kernel), and the one chain both recoveries run (recover_chain).
+// selection uses (free_space_kernel), and the one chain the recoveries run (recover_chain).  The points come from
+// depth images (sqr_lsq_*, sqr_least_squares_normal_eq) or from point lists (sqr_pts_*): see "point sources".
 #include "sqr_common.h"
 #include "sqr_sq_dev.h"
+
+#include <type_traits>
 
 namespace sqr {
 
@@ -59,12 +62,66 @@ __device__ __forceinline__ void lsq_point_row(const SQ& s, float dx, float dy, f
   row[13] = row[14] = row[15] = 0.f;
 }
 
-// grid: (blocks_per_sample, S); one thread per resized pixel.  partials: [S][nblk][16][16] float64.  Sample b
-// reads image b mod Bimg (the batched multi-start refinement's [K,Bimg] layout; Bimg = S: one image each)
-template <int NT>
-__global__ void __launch_bounds__(NT) lsq_normal_eq_kernel(const float* __restrict__ params,
-                                                           const float* __restrict__ target, int Bimg, int H, int W,
-                                                           int R, double* __restrict__ partials) {
+// the point (c / R, 1 - r / R, z) of resized pixel `pix` of image b and whether it counts (z > 0: false for
+// NaN); the resize arithmetic of least_squares_kernel
+__device__ __forceinline__ bool lsq_point(const float* __restrict__ target, int b, int H, int W, int R, int pix,
+                                          float& x, float& y, float& z) {
+  x = y = z = 0.f;
+  if (pix >= R * R) return false;
+  const int r = pix / R, c = pix - r * R;
+  const float sh = (float)H / (float)R, sw = (float)W / (float)R;
+  const int sr = min((int)floorf((float)r * sh), H - 1);
+  const int sc = min((int)floorf((float)c * sw), W - 1);
+  z = target[((size_t)b * H + sr) * W + sc];
+  x = (float)c / (float)R;
+  y = 1.f - (float)r / (float)R;
+  return z > 0.f;
+}
+
+// -------------------------------------------------------------------------- point sources
+// Where the point-reading kernels (lsq_normal_eq_kernel, lsq_moments_kernel, lsq_extents_kernel) take slot i of
+// sample b from: point(b, i, x, y, z) gives the fp32 point and whether it counts (a slot that does not is a zero
+// row, a zero moment term, and ignored by min / max), slots() the slots per sample (one thread each, slot i =
+// thread i mod 256 of block i / 256), nsrc() the images / clouds (sample s of a [K,nsrc] stack reads s mod nsrc).
+// The kernels are templates on the source, so each source has its own straight-line code.
+struct ImageSrc {  // the resized pixels of [Bimg,H,W] depth images in pixel order: lsq_point
+  const float* target;
+  int Bimg, H, W, R;
+  __host__ __device__ int nsrc() const { return Bimg; }
+  __host__ __device__ size_t slots() const { return (size_t)R * R; }
+  __device__ __forceinline__ bool point(int b, int i, float& x, float& y, float& z) const {
+    return lsq_point(target, b, H, W, R, i, x, y, z);
+  }
+};
+
+// A point list: points [B,P,3] f32 (x, y, z), count [B] i32 (nullable: every cloud has P slots).  Slot i of cloud
+// b counts iff i < count[b] (clamped into [0, P]) and all three coordinates are finite; no range is imposed on
+// them (z <= 0 is an ordinary point).
+struct ListSrc {
+  const float* points;
+  const int* count;
+  int B, P;
+  __host__ __device__ int nsrc() const { return B; }
+  __host__ __device__ size_t slots() const { return (size_t)P; }
+  __device__ __forceinline__ bool point(int b, int i, float& x, float& y, float& z) const {
+    x = y = z = 0.f;
+    const int n = count ? min(max(count[b], 0), P) : P;
+    if (i >= n) return false;
+    const float* p = points + ((size_t)b * P + i) * 3;
+    const float px = p[0], py = p[1], pz = p[2];
+    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return false;
+    x = px;
+    y = py;
+    z = pz;
+    return true;
+  }
+};
+
+// grid: (blocks_per_sample, S); one thread per slot of the source.  partials: [S][nblk][16][16] float64.  Sample b
+// reads image / cloud b mod nsrc (the batched multi-start refinement's [K,nsrc] layout; nsrc = S: one each)
+template <int NT, class Src>
+__global__ void __launch_bounds__(NT) lsq_normal_eq_kernel(const float* __restrict__ params, const Src src,
+                                                           double* __restrict__ partials) {
   static_assert(NT == kNeqP, "one thread per entry of the block's Gram matrix");
   typedef double d4 __attribute__((ext_vector_type(4)));
   __shared__ float4 tile[NT / 64][64 * kNeqT / 4];
@@ -76,19 +133,9 @@ __global__ void __launch_bounds__(NT) lsq_normal_eq_kernel(const float* __restri
   float row[kNeqT];
 #pragma unroll
   for (int i = 0; i < kNeqT; ++i) row[i] = 0.f;
-  const int pix = blockIdx.x * NT + threadIdx.x;
-  if (pix < R * R) {
-    const int r = pix / R, c = pix - r * R;
-    // F.interpolate nearest (float scale, floor, clamp), as least_squares_kernel
-    const float sh = (float)H / (float)R, sw = (float)W / (float)R;
-    const int sr = min((int)floorf((float)r * sh), H - 1);
-    const int sc = min((int)floorf((float)c * sw), W - 1);
-    const float z = target[((size_t)(b % Bimg) * H + sr) * W + sc];
-    if (z > 0.f) {  // classes.py:363 (false for NaN)
-      const float gx = (float)c / (float)R, gy = 1.f - (float)r / (float)R;
-      lsq_point_row(s, gx - s.t[0], gy - s.t[1], z - s.t[2], row);
-    }
-  }
+  float gx, gy, z;
+  if (src.point(b % src.nsrc(), blockIdx.x * NT + threadIdx.x, gx, gy, z))
+    lsq_point_row(s, gx - s.t[0], gy - s.t[1], z - s.t[2], row);
 #pragma unroll
   for (int i = 0; i < kNeqT / 4; ++i)
     tile[wid][lane * (kNeqT / 4) + i] = make_float4(row[4 * i], row[4 * i + 1], row[4 * i + 2], row[4 * i + 3]);
@@ -285,32 +332,15 @@ __global__ void __launch_bounds__(64) lm_step_kernel(int B, int accept, int solv
 constexpr int kMomN = 10;         // upper triangle of the Gram matrix of the rows [x y z 1]: xx xy xz x yy yz y zz z n
 constexpr int kJacobiSweeps = 8;  // cyclic Jacobi on a 3 x 3 converges quadratically: 4-5 sweeps reach an ulp
 
-// the point (c / R, 1 - r / R, z) of resized pixel `pix` of image b and whether it counts (z > 0: false for
-// NaN); the resize arithmetic of least_squares_kernel
-__device__ __forceinline__ bool lsq_point(const float* __restrict__ target, int b, int H, int W, int R, int pix,
-                                          float& x, float& y, float& z) {
-  x = y = z = 0.f;
-  if (pix >= R * R) return false;
-  const int r = pix / R, c = pix - r * R;
-  const float sh = (float)H / (float)R, sw = (float)W / (float)R;
-  const int sr = min((int)floorf((float)r * sh), H - 1);
-  const int sc = min((int)floorf((float)c * sw), W - 1);
-  z = target[((size_t)b * H + sr) * W + sc];
-  x = (float)c / (float)R;
-  y = 1.f - (float)r / (float)R;
-  return z > 0.f;
-}
-
-// grid: (blocks_per_sample, B); one thread per resized pixel.  partials: [B][nblk][kMomN] float64.  The
+// grid: (blocks_per_sample, B); one thread per slot of the source.  partials: [B][nblk][kMomN] float64.  The
 // products of two floats are exact in float64; lanes are summed by DPP (wave_sum_d), waves in order, as
 // least_squares_kernel does, so the sums are bitwise defined.  A pixel that does not count is a zero row.
-template <int NT>
-__global__ void __launch_bounds__(NT) lsq_moments_kernel(const float* __restrict__ target, int H, int W, int R,
-                                                         double* __restrict__ partials) {
+template <int NT, class Src>
+__global__ void __launch_bounds__(NT) lsq_moments_kernel(const Src src, double* __restrict__ partials) {
   __shared__ double red[(NT / 64) * kMomN];
   const int b = blockIdx.y;
   float fx, fy, fz;
-  const bool on = lsq_point(target, b, H, W, R, blockIdx.x * NT + threadIdx.x, fx, fy, fz);
+  const bool on = src.point(b, blockIdx.x * NT + threadIdx.x, fx, fy, fz);
   const double x = on ? (double)fx : 0.0, y = on ? (double)fy : 0.0, z = on ? (double)fz : 0.0;
   const double one = on ? 1.0 : 0.0;
   const double vals[kMomN] = {x * x, x * y, x * z, x, y * y, y * z, y, z * z, z, one};
@@ -437,18 +467,17 @@ __global__ void __launch_bounds__(64) lsq_frame_kernel(const double* __restrict_
   V[6] = v20; V[7] = v21; V[8] = v22;
 }
 
-// grid: (blocks_per_sample, B); one thread per resized pixel, float64.  partials: [B][nblk][6] = the block's
+// grid: (blocks_per_sample, B); one thread per slot of the source, float64.  partials: [B][nblk][6] = the block's
 // minimum (0..2) and maximum (3..5) of V^T p along the three axes over its counted points (+inf / -inf where
 // it has none).  min and max do not depend on the order: any reduction is bitwise reproducible.
-template <int NT>
-__global__ void __launch_bounds__(NT) lsq_extents_kernel(const float* __restrict__ target, int H, int W, int R,
-                                                         const double* __restrict__ frame,
+template <int NT, class Src>
+__global__ void __launch_bounds__(NT) lsq_extents_kernel(const Src src, const double* __restrict__ frame,
                                                          double* __restrict__ partials) {
   __shared__ double red[(NT / 64) * 6];
   const int b = blockIdx.y;
   const double* V = frame + 9 * (size_t)b;
   float fx, fy, fz;
-  const bool on = lsq_point(target, b, H, W, R, blockIdx.x * NT + threadIdx.x, fx, fy, fz);
+  const bool on = src.point(b, blockIdx.x * NT + threadIdx.x, fx, fy, fz);
   double v[6];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -716,19 +745,45 @@ __global__ void __launch_bounds__(64) lsq_gather_kernel(int B, const int* __rest
 using namespace sqr;
 
 // ============================================================================ C ABI
-static size_t normal_eq_blocks(int R) { return ((size_t)R * R + kNeqP - 1) / kNeqP; }
+// Blocks of 256 slots per sample: the grid of every launch over a source (kNeqP = 256 too).  The byte counts below
+// are written on the slots per sample, R^2 for images and P for point lists, so that both sources share them.
+static_assert(kNeqP == 256, "the normal equations and the starts share one block count");
+static size_t slot_blocks(size_t slots) { return (slots + 255) / 256; }
+static size_t image_slots(int R) { return (size_t)R * R; }
+constexpr int kMaxListSlots = 1 << 20;  // P of a point list: the slots of R = 1024
+
+static size_t normal_eq_bytes(size_t S, size_t slots) { return S * slot_blocks(slots) * kNeqP * sizeof(double); }
 
 extern "C" size_t sqr_least_squares_normal_eq_workspace_bytes(int B, int R) {
   if (B <= 0 || R <= 0) return 0;
-  return (size_t)B * normal_eq_blocks(R) * kNeqP * sizeof(double);
+  return normal_eq_bytes((size_t)B, image_slots(R));
 }
 
-// the two launches of the normal equations (arguments checked by the callers)
-static int launch_normal_eq(hipStream_t st, const float* params, const float* target, int B, int Bimg, int H, int W,
-                            int R, double* JtJ, double* Jtr, double* energy, double* energy_copy, double* partials) {
-  const int nblk = (int)normal_eq_blocks(R);
-  hipLaunchKernelGGL((lsq_normal_eq_kernel<kNeqP>), dim3(nblk, B), dim3(kNeqP), 0, st, params, target, Bimg, H, W, R,
-                     partials);
+extern "C" size_t sqr_pts_normal_eq_workspace_bytes(int S, int P) {
+  if (S <= 0 || P <= 0) return 0;
+  return normal_eq_bytes((size_t)S, (size_t)P);
+}
+
+// What an entry checks of its source before anything else, `who` the entry's name in the messages
+static int check_source(const char* who, const ImageSrc& src) {
+  SQR_CHECK_ARG(src.R >= 1 && src.R <= 1024, "%s: R=%d out of range [1,1024]", who, src.R);
+  SQR_CHECK_ARG(src.H >= 1 && src.W >= 1, "%s: bad target size %dx%d", who, src.H, src.W);
+  SQR_CHECK_ARG(src.target, "%s: null pointer", who);
+  return SQR_OK;
+}
+
+static int check_source(const char* who, const ListSrc& src) {
+  SQR_CHECK_ARG(src.P >= 1 && src.P <= kMaxListSlots, "%s: P=%d out of range [1,%d]", who, src.P, kMaxListSlots);
+  SQR_CHECK_ARG(src.points, "%s: null pointer", who);
+  return SQR_OK;
+}
+
+// the two launches of the normal equations over B samples (arguments checked by the callers)
+template <class Src>
+static int launch_normal_eq(hipStream_t st, const float* params, const Src& src, int B, double* JtJ, double* Jtr,
+                            double* energy, double* energy_copy, double* partials) {
+  const int nblk = (int)slot_blocks(src.slots());
+  hipLaunchKernelGGL((lsq_normal_eq_kernel<kNeqP, Src>), dim3(nblk, B), dim3(kNeqP), 0, st, params, src, partials);
   SQR_HIP_LAUNCH_CHECK("lsq_normal_eq_kernel");
   hipLaunchKernelGGL(lsq_normal_eq_finalize_kernel, dim3(B), dim3(kNeqP), 0, st, params, partials, nblk, JtJ, Jtr,
                      energy, energy_copy);
@@ -748,8 +803,22 @@ extern "C" int sqr_least_squares_normal_eq(const float* params, const float* tar
     set_error("least_squares_normal_eq: workspace %zu < %zu bytes", workspace_bytes, need);
     return SQR_E_WORKSPACE;
   }
-  return launch_normal_eq(as_stream(stream), params, target, B, B, H, W, R, JtJ, Jtr, energy, nullptr,
+  return launch_normal_eq(as_stream(stream), params, ImageSrc{target, B, H, W, R}, B, JtJ, Jtr, energy, nullptr,
                           (double*)workspace);
+}
+
+extern "C" int sqr_pts_normal_eq(const float* params, const float* points, const int* count, int S, int B, int P,
+                                 double* JtJ, double* Jtr, double* energy, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  SQR_CHECK_ARG(B >= 1 && S >= B && S <= 65535 && S % B == 0,
+                "pts_normal_eq: S=%d must be a multiple of B=%d in [B,65535]", S, B);
+  const ListSrc src{points, count, B, P};
+  const int rc = check_source("pts_normal_eq", src);
+  if (rc != SQR_OK) return rc;
+  SQR_CHECK_ARG(params && JtJ && Jtr && energy && workspace, "pts_normal_eq: null pointer");
+  const size_t need = sqr_pts_normal_eq_workspace_bytes(S, P);
+  SQR_CHECK_ARG(workspace_bytes >= need, "pts_normal_eq: workspace %zu < %zu bytes", workspace_bytes, need);
+  return launch_normal_eq(as_stream(stream), params, src, S, JtJ, Jtr, energy, nullptr, (double*)workspace);
 }
 
 extern "C" int sqr_lsq_lm_step(int B, int accept, int solve, double up, double down, float* params, double* JtJ,
@@ -774,18 +843,27 @@ extern "C" int sqr_lsq_lm_step(int B, int accept, int solve, double up, double d
 // per sample, the normal equations' partials, params_trial [B,12] f32
 constexpr size_t kLmDoubles = 144 + 12 + 1 + 144 + 12 + 1 + 12;
 
-extern "C" size_t sqr_lsq_lm_refine_workspace_bytes(int B, int R) {
-  if (B <= 0 || R <= 0) return 0;
-  return (size_t)B * kLmDoubles * sizeof(double) + sqr_least_squares_normal_eq_workspace_bytes(B, R) +
-         (size_t)B * 12 * sizeof(float);
+static size_t lm_refine_bytes(size_t S, size_t slots) {
+  return S * kLmDoubles * sizeof(double) + normal_eq_bytes(S, slots) + S * 12 * sizeof(float);
 }
 
-// The chain of sqr_lsq_lm_refine over B samples, sample b on image b mod Bimg (arguments checked by the callers;
-// the workspace is sqr_lsq_lm_refine_workspace_bytes(B, R)).  Every sample is on its own and every sum has a
+extern "C" size_t sqr_lsq_lm_refine_workspace_bytes(int B, int R) {
+  if (B <= 0 || R <= 0) return 0;
+  return lm_refine_bytes((size_t)B, image_slots(R));
+}
+
+extern "C" size_t sqr_pts_lm_refine_workspace_bytes(int S, int P) {
+  if (S <= 0 || P <= 0) return 0;
+  return lm_refine_bytes((size_t)S, (size_t)P);
+}
+
+// The chain of sqr_lsq_lm_refine over B samples, sample b on image / cloud b mod src.nsrc() (arguments checked by
+// the callers; the workspace is lm_refine_bytes(B, src.slots())).  Every sample is on its own and every sum has a
 // fixed order, so a sample's result does not depend on B.
-static int lm_refine_chain(const float* params_in, const float* target, int B, int Bimg, int H, int W, int R, int iters,
-                           double lambda0, double up, double down, float* params_out, double* energy_before,
-                           double* energy_after, int* accepted, void* workspace, void* stream) {
+template <class Src>
+static int lm_refine_chain(const float* params_in, const Src& src, int B, int iters, double lambda0, double up,
+                           double down, float* params_out, double* energy_before, double* energy_after,
+                           int* accepted, void* workspace, void* stream) {
   hipStream_t st = as_stream(stream);
   const size_t nb = (size_t)B;
   double* JtJ = (double*)workspace;
@@ -796,11 +874,11 @@ static int lm_refine_chain(const float* params_in, const float* target, int B, i
   double* E_t = Jtr_t + 12 * nb;
   double* delta = E_t + nb;
   double* partials = delta + 12 * nb;
-  float* p_t = (float*)(partials + nb * normal_eq_blocks(R) * kNeqP);
+  float* p_t = (float*)(partials + nb * slot_blocks(src.slots()) * kNeqP);
   hipLaunchKernelGGL(lm_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, params_in, B, lambda0, params_out, lambda,
                      accepted);
   SQR_HIP_LAUNCH_CHECK("lm_init_kernel");
-  int rc = launch_normal_eq(st, params_out, target, B, Bimg, H, W, R, JtJ, Jtr, energy_after, energy_before, partials);
+  int rc = launch_normal_eq(st, params_out, src, B, JtJ, Jtr, energy_after, energy_before, partials);
   if (rc != SQR_OK) return rc;
   for (int it = 0; it <= iters && iters > 0; ++it) {
     // round it: accept the trial of the round before (none in round 0), solve for the next one and
@@ -810,31 +888,32 @@ static int lm_refine_chain(const float* params_in, const float* target, int B, i
                          E_t, delta, accepted, stream);
     if (rc != SQR_OK) return rc;
     if (solve) {
-      rc = launch_normal_eq(st, p_t, target, B, Bimg, H, W, R, JtJ_t, Jtr_t, E_t, nullptr, partials);
+      rc = launch_normal_eq(st, p_t, src, B, JtJ_t, Jtr_t, E_t, nullptr, partials);
       if (rc != SQR_OK) return rc;
     }
   }
   return SQR_OK;
 }
 
-// Both refinement entries behind their own batch bound, `who` the entry's name in the messages: K slices of B
+// The refinement entries behind their own batch bound, `who` the entry's name in the messages: K slices of B
 // samples in one chain (sqr_lsq_lm_refine: K = 1)
-static int lm_refine_entry(const char* who, const float* params_in, const float* target, int K, int B, int H, int W,
-                           int R, int iters, double lambda0, double up, double down, float* params_out,
-                           double* energy_before, double* energy_after, int* accepted, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  SQR_CHECK_ARG(R >= 1 && R <= 1024, "%s: R=%d out of range [1,1024]", who, R);
-  SQR_CHECK_ARG(H >= 1 && W >= 1, "%s: bad target size %dx%d", who, H, W);
+template <class Src>
+static int lm_refine_entry(const char* who, const float* params_in, const Src& src, int K, int B, int iters,
+                           double lambda0, double up, double down, float* params_out, double* energy_before,
+                           double* energy_after, int* accepted, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  const int rc = check_source(who, src);
+  if (rc != SQR_OK) return rc;
   SQR_CHECK_ARG(iters >= 0, "%s: iters=%d must be >= 0", who, iters);
   SQR_CHECK_ARG(lambda0 > 0.0, "%s: lambda0=%g must be > 0", who, lambda0);
   SQR_CHECK_ARG(up > 1.0, "%s: up=%g must be > 1", who, up);
   SQR_CHECK_ARG(down > 0.0 && down < 1.0, "%s: down=%g outside (0,1)", who, down);
-  SQR_CHECK_ARG(params_in && target && params_out && energy_before && energy_after && accepted && workspace,
+  SQR_CHECK_ARG(params_in && params_out && energy_before && energy_after && accepted && workspace,
                 "%s: null pointer", who);
-  const size_t need = sqr_lsq_lm_refine_workspace_bytes(K * B, R);
+  const size_t need = lm_refine_bytes((size_t)K * B, src.slots());
   SQR_CHECK_ARG(workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-  return lm_refine_chain(params_in, target, K * B, B, H, W, R, iters, lambda0, up, down, params_out, energy_before,
-                         energy_after, accepted, workspace, stream);
+  return lm_refine_chain(params_in, src, K * B, iters, lambda0, up, down, params_out, energy_before, energy_after,
+                         accepted, workspace, stream);
 }
 
 extern "C" int sqr_lsq_lm_refine(const float* params_in, const float* target, int B, int H, int W, int R, int iters,
@@ -842,8 +921,8 @@ extern "C" int sqr_lsq_lm_refine(const float* params_in, const float* target, in
                                  double* energy_after, int* accepted, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   SQR_CHECK_ARG(B >= 1 && B <= 65535, "lsq_lm_refine: B=%d out of range [1,65535]", B);
-  return lm_refine_entry("lsq_lm_refine", params_in, target, 1, B, H, W, R, iters, lambda0, up, down, params_out,
-                         energy_before, energy_after, accepted, workspace, workspace_bytes, stream);
+  return lm_refine_entry("lsq_lm_refine", params_in, ImageSrc{target, B, H, W, R}, 1, B, iters, lambda0, up, down,
+                         params_out, energy_before, energy_after, accepted, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sqr_lsq_lm_refine_multi(const float* params_in, const float* target, int K, int B, int H, int W, int R,
@@ -852,32 +931,46 @@ extern "C" int sqr_lsq_lm_refine_multi(const float* params_in, const float* targ
                                        size_t workspace_bytes, void* stream) {
   SQR_CHECK_ARG(K >= 1 && B >= 1 && (long long)K * B <= 65535, "lsq_lm_refine_multi: K=%d x B=%d out of range [1,65535]",
                 K, B);
-  return lm_refine_entry("lsq_lm_refine_multi", params_in, target, K, B, H, W, R, iters, lambda0, up, down, params_out,
-                         energy_before, energy_after, accepted, workspace, workspace_bytes, stream);
+  return lm_refine_entry("lsq_lm_refine_multi", params_in, ImageSrc{target, B, H, W, R}, K, B, iters, lambda0, up,
+                         down, params_out, energy_before, energy_after, accepted, workspace, workspace_bytes, stream);
 }
 
-// blocks of 256 resized pixels per sample: the starts' and the free-space energy's launches
-static size_t pixel_blocks(int R) { return ((size_t)R * R + 255) / 256; }
+extern "C" int sqr_pts_lm_refine(const float* params_in, const float* points, const int* count, int K, int B, int P,
+                                 int iters, double lambda0, double up, double down, float* params_out,
+                                 double* energy_before, double* energy_after, int* accepted, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(K >= 1 && B >= 1 && (long long)K * B <= 65535, "pts_lm_refine: K=%d x B=%d out of range [1,65535]", K,
+                B);
+  return lm_refine_entry("pts_lm_refine", params_in, ListSrc{points, count, B, P}, K, B, iters, lambda0, up, down,
+                         params_out, energy_before, energy_after, accepted, workspace, workspace_bytes, stream);
+}
 
 // the moments' partials [B][nblk][kMomN], then the extents' [B][nblk][6], float64
+static size_t starts_bytes(size_t B, size_t slots) { return B * slot_blocks(slots) * (kMomN + 6) * sizeof(double); }
+
 extern "C" size_t sqr_lsq_starts_workspace_bytes(int B, int R) {
   if (B <= 0 || R <= 0) return 0;
-  return (size_t)B * pixel_blocks(R) * (kMomN + 6) * sizeof(double);
+  return starts_bytes((size_t)B, image_slots(R));
+}
+
+extern "C" size_t sqr_pts_starts_workspace_bytes(int B, int P) {
+  if (B <= 0 || P <= 0) return 0;
+  return starts_bytes((size_t)B, (size_t)P);
 }
 
 // the four launches of the starts (arguments checked by the callers)
-static int launch_starts(hipStream_t st, const float* target, int B, int H, int W, int R, int nsets, float e0,
-                         float depth, float* starts, int* count, double* centroid, double* eigenvalues, double* frame,
-                         double* workspace) {
-  const int nblk = (int)pixel_blocks(R);
+template <class Src>
+static int launch_starts(hipStream_t st, const Src& src, int B, int nsets, float e0, float depth, float* starts,
+                         int* count, double* centroid, double* eigenvalues, double* frame, double* workspace) {
+  const int nblk = (int)slot_blocks(src.slots());
   double* mom = workspace;
   double* ext = mom + (size_t)B * nblk * kMomN;
-  hipLaunchKernelGGL((lsq_moments_kernel<256>), dim3(nblk, B), dim3(256), 0, st, target, H, W, R, mom);
+  hipLaunchKernelGGL((lsq_moments_kernel<256, Src>), dim3(nblk, B), dim3(256), 0, st, src, mom);
   SQR_HIP_LAUNCH_CHECK("lsq_moments_kernel");
   hipLaunchKernelGGL(lsq_frame_kernel, dim3((B + 63) / 64), dim3(64), 0, st, mom, B, nblk, count, centroid,
                      eigenvalues, frame);
   SQR_HIP_LAUNCH_CHECK("lsq_frame_kernel");
-  hipLaunchKernelGGL((lsq_extents_kernel<256>), dim3(nblk, B), dim3(256), 0, st, target, H, W, R, frame, ext);
+  hipLaunchKernelGGL((lsq_extents_kernel<256, Src>), dim3(nblk, B), dim3(256), 0, st, src, frame, ext);
   SQR_HIP_LAUNCH_CHECK("lsq_extents_kernel");
   hipLaunchKernelGGL(lsq_starts_kernel, dim3((3 * nsets * B + 63) / 64), dim3(64), 0, st, B, nblk, nsets, e0, depth,
                      count, frame, ext, starts);
@@ -885,34 +978,42 @@ static int launch_starts(hipStream_t st, const float* target, int B, int H, int 
   return SQR_OK;
 }
 
-// nsets = 1: sqr_lsq_starts (depth 0), 2: sqr_lsq_starts6
-static int starts_entry(const char* who, const float* target, int B, int H, int W, int R, int nsets, float e0,
-                        float depth, float* starts, int* count, double* centroid, double* eigenvalues, double* frame,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+// nsets = 1: sqr_lsq_starts and sqr_pts_starts (depth 0), 2: sqr_lsq_starts6
+template <class Src>
+static int starts_entry(const char* who, const Src& src, int B, int nsets, float e0, float depth, float* starts,
+                        int* count, double* centroid, double* eigenvalues, double* frame, void* workspace,
+                        size_t workspace_bytes, void* stream) {
   SQR_CHECK_ARG(B >= 1 && B <= 65535, "%s: B=%d out of range [1,65535]", who, B);
-  SQR_CHECK_ARG(R >= 1 && R <= 1024, "%s: R=%d out of range [1,1024]", who, R);
-  SQR_CHECK_ARG(H >= 1 && W >= 1, "%s: bad target size %dx%d", who, H, W);
+  const int rc = check_source(who, src);
+  if (rc != SQR_OK) return rc;
   SQR_CHECK_ARG(e0 >= 0.1f && e0 <= 1.f, "%s: e0=%g outside [0.1,1]", who, (double)e0);
   SQR_CHECK_ARG(depth >= 0.f && depth <= 8.f, "%s: depth=%g outside [0,8]", who, (double)depth);
-  SQR_CHECK_ARG(target && starts && count && centroid && eigenvalues && frame && workspace, "%s: null pointer", who);
-  const size_t need = sqr_lsq_starts_workspace_bytes(B, R);
+  SQR_CHECK_ARG(starts && count && centroid && eigenvalues && frame && workspace, "%s: null pointer", who);
+  const size_t need = starts_bytes((size_t)B, src.slots());
   SQR_CHECK_ARG(workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-  return launch_starts(as_stream(stream), target, B, H, W, R, nsets, e0, depth, starts, count, centroid, eigenvalues,
-                       frame, (double*)workspace);
+  return launch_starts(as_stream(stream), src, B, nsets, e0, depth, starts, count, centroid, eigenvalues, frame,
+                       (double*)workspace);
 }
 
 extern "C" int sqr_lsq_starts(const float* target, int B, int H, int W, int R, float e0, float* starts, int* count,
                               double* centroid, double* eigenvalues, double* frame, void* workspace,
                               size_t workspace_bytes, void* stream) {
-  return starts_entry("lsq_starts", target, B, H, W, R, 1, e0, 0.f, starts, count, centroid, eigenvalues, frame,
-                      workspace, workspace_bytes, stream);
+  return starts_entry("lsq_starts", ImageSrc{target, B, H, W, R}, B, 1, e0, 0.f, starts, count, centroid, eigenvalues,
+                      frame, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sqr_pts_starts(const float* points, const int* count, int B, int P, float e0, float* starts,
+                              int* count_out, double* centroid, double* eigenvalues, double* frame, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  return starts_entry("pts_starts", ListSrc{points, count, B, P}, B, 1, e0, 0.f, starts, count_out, centroid,
+                      eigenvalues, frame, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sqr_lsq_starts6(const float* target, int B, int H, int W, int R, float e0, float depth, float* starts,
                                int* count, double* centroid, double* eigenvalues, double* frame, void* workspace,
                                size_t workspace_bytes, void* stream) {
-  return starts_entry("lsq_starts6", target, B, H, W, R, 2, e0, depth, starts, count, centroid, eigenvalues, frame,
-                      workspace, workspace_bytes, stream);
+  return starts_entry("lsq_starts6", ImageSrc{target, B, H, W, R}, B, 2, e0, depth, starts, count, centroid,
+                      eigenvalues, frame, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sqr_lsq_select(int B, int K, const float* params, const double* energy, float* out_params,
@@ -928,14 +1029,14 @@ extern "C" int sqr_lsq_select(int B, int K, const float* params, const double* e
 
 extern "C" size_t sqr_lsq_free_space_workspace_bytes(int S, int R) {
   if (S <= 0 || R <= 0) return 0;
-  return (size_t)S * pixel_blocks(R) * sizeof(double);
+  return (size_t)S * slot_blocks(image_slots(R)) * sizeof(double);
 }
 
 // the two launches of the free-space energy (arguments checked by the callers)
 static int launch_free_space(hipStream_t st, const float* params, const float* target, int S, int B, int H, int W,
                              int R, float margin, double* energy_fs, const double* energy, double w, double* score,
                              double* partials) {
-  const int nblk = (int)pixel_blocks(R);
+  const int nblk = (int)slot_blocks(image_slots(R));
   hipLaunchKernelGGL((free_space_kernel<256>), dim3(nblk, S), dim3(256), 0, st, params, target, B, H, W, R, margin,
                      partials);
   SQR_HIP_LAUNCH_CHECK("free_space_kernel");
@@ -966,14 +1067,23 @@ extern "C" int sqr_lsq_free_space(const float* params, const float* target, int 
 // (sqr_lsq_recover, which does not return them) the starts [3,B,12] f32, then count [B] i32.
 constexpr size_t kRecoverDoubles = 3 + 3 + 9;
 
-static size_t recover_region_bytes(int K, int B, int R) {
-  const size_t a = sqr_lsq_starts_workspace_bytes(B, R), b = sqr_lsq_lm_refine_workspace_bytes(K * B, R);
+static size_t recover_region_bytes(size_t K, size_t B, size_t slots) {
+  const size_t a = starts_bytes(B, slots), b = lm_refine_bytes(K * B, slots);
   return a > b ? a : b;
+}
+
+static size_t recover_bytes(size_t K, size_t B, size_t slots) {
+  return B * kRecoverDoubles * sizeof(double) + recover_region_bytes(K, B, slots) + B * sizeof(int);
 }
 
 extern "C" size_t sqr_lsq_recover_multi_workspace_bytes(int K, int B, int R) {
   if (K <= 0 || B <= 0 || R <= 0) return 0;
-  return (size_t)B * kRecoverDoubles * sizeof(double) + recover_region_bytes(K, B, R) + (size_t)B * sizeof(int);
+  return recover_bytes((size_t)K, (size_t)B, image_slots(R));
+}
+
+extern "C" size_t sqr_pts_recover_workspace_bytes(int K, int B, int P) {
+  if (K <= 0 || B <= 0 || P <= 0) return 0;
+  return recover_bytes((size_t)K, (size_t)B, (size_t)P);
 }
 
 extern "C" size_t sqr_lsq_recover_workspace_bytes(int B, int R) {
@@ -981,43 +1091,51 @@ extern "C" size_t sqr_lsq_recover_workspace_bytes(int B, int R) {
   return sqr_lsq_recover_multi_workspace_bytes(3, B, R) + (size_t)B * 3 * 12 * sizeof(float);
 }
 
-// Both recoveries behind their own batch bounds, `who` the entry's name in the messages: the starts (nstarts = 3 or
+// The scored selection's arguments and outputs (sqr_lsq_recover_multi): an image source only, a list has no rays
+struct FreeSpaceSel {
+  double w_fs;
+  float margin;
+  double *energy_fs_out, *all_fs, *all_score;
+};
+
+// The recoveries behind their own batch bounds, `who` the entry's name in the messages: the starts (nstarts = 3 or
 // 6), the caller's Kx extra ones behind them, one refinement chain over all K B samples, K = nstarts + Kx, and the
-// selection: scored, on all_after + w_fs all_fs (all_starts, all_fs, all_score, energy_fs_out are outputs), or on
-// all_after (they are NULL, and the starts stay in the workspace).
-static int recover_chain(const char* who, bool scored, const float* target, int B, int H, int W, int R, int iters,
-                         int nstarts, float e0, float depth, const float* extra, int Kx, double lambda0, double up,
-                         double down, double w_fs, float margin, float* params_out, double* energy_out,
-                         double* energy_fs_out, int* index_out, float* all_starts, float* all_params,
-                         double* all_before, double* all_after, double* all_fs, double* all_score, int* all_accepted,
-                         void* workspace, size_t workspace_bytes, void* stream) {
+// selection: scored (fs != NULL; images), on all_after + w_fs all_fs, or on all_after.  all_starts NULL: the starts
+// stay in the workspace.
+template <class Src>
+static int recover_chain(const char* who, const FreeSpaceSel* fs, const Src& src, int B, int iters, int nstarts,
+                         float e0, float depth, const float* extra, int Kx, double lambda0, double up, double down,
+                         float* params_out, double* energy_out, int* index_out, float* all_starts, float* all_params,
+                         double* all_before, double* all_after, int* all_accepted, void* workspace,
+                         size_t workspace_bytes, void* stream) {
   const int K = nstarts + Kx;
   const size_t nb = (size_t)B, own_starts = all_starts ? 0 : (size_t)K * nb * 12 * sizeof(float);
-  SQR_CHECK_ARG(R >= 1 && R <= 1024, "%s: R=%d out of range [1,1024]", who, R);
-  SQR_CHECK_ARG(H >= 1 && W >= 1, "%s: bad target size %dx%d", who, H, W);
+  int rc = check_source(who, src);
+  if (rc != SQR_OK) return rc;
   SQR_CHECK_ARG(iters >= 0, "%s: iters=%d must be >= 0", who, iters);
   SQR_CHECK_ARG(e0 >= 0.1f && e0 <= 1.f, "%s: e0=%g outside [0.1,1]", who, (double)e0);
   SQR_CHECK_ARG(depth >= 0.f && depth <= 8.f, "%s: depth=%g outside [0,8]", who, (double)depth);
   SQR_CHECK_ARG(lambda0 > 0.0, "%s: lambda0=%g must be > 0", who, lambda0);
   SQR_CHECK_ARG(up > 1.0, "%s: up=%g must be > 1", who, up);
   SQR_CHECK_ARG(down > 0.0 && down < 1.0, "%s: down=%g outside (0,1)", who, down);
-  SQR_CHECK_ARG(w_fs >= 0.0 && w_fs <= 1e300, "%s: w_fs=%g must be a finite number >= 0", who, w_fs);
-  SQR_CHECK_ARG(margin >= 0.f, "%s: margin=%g must be >= 0", who, (double)margin);
-  SQR_CHECK_ARG(target && params_out && energy_out && index_out && all_params && all_before && all_after &&
-                    all_accepted && workspace && (!scored || (energy_fs_out && all_starts && all_fs && all_score)),
+  SQR_CHECK_ARG(!fs || (fs->w_fs >= 0.0 && fs->w_fs <= 1e300), "%s: w_fs=%g must be a finite number >= 0", who,
+                fs->w_fs);
+  SQR_CHECK_ARG(!fs || fs->margin >= 0.f, "%s: margin=%g must be >= 0", who, (double)fs->margin);
+  SQR_CHECK_ARG(params_out && energy_out && index_out && all_params && all_before && all_after && all_accepted &&
+                    workspace && (!fs || (fs->energy_fs_out && all_starts && fs->all_fs && fs->all_score)),
                 "%s: null pointer", who);
-  const size_t need = sqr_lsq_recover_multi_workspace_bytes(K, B, R) + own_starts;
+  const size_t need = recover_bytes((size_t)K, nb, src.slots()) + own_starts;
   SQR_CHECK_ARG(workspace_bytes >= need, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
   hipStream_t st = as_stream(stream);
   double* centroid = (double*)workspace;
   double* eigenvalues = centroid + 3 * nb;
   double* frame = eigenvalues + 3 * nb;
   char* region = (char*)(frame + 9 * nb);
-  char* tail = region + recover_region_bytes(K, B, R);
+  char* tail = region + recover_region_bytes((size_t)K, nb, src.slots());
   if (!all_starts) all_starts = (float*)tail;
   int* count = (int*)(tail + own_starts);
-  int rc = launch_starts(st, target, B, H, W, R, nstarts / 3, e0, depth, all_starts, count, centroid, eigenvalues,
-                         frame, (double*)region);
+  rc = launch_starts(st, src, B, nstarts / 3, e0, depth, all_starts, count, centroid, eigenvalues, frame,
+                     (double*)region);
   if (rc != SQR_OK) return rc;
   if (Kx > 0) {
     const long long n = (long long)Kx * B * 12;
@@ -1025,20 +1143,24 @@ static int recover_chain(const char* who, bool scored, const float* target, int 
                        all_starts + 12 * nb * nstarts);
     SQR_HIP_LAUNCH_CHECK("lsq_copy_kernel");
   }
-  rc = lm_refine_chain(all_starts, target, K * B, B, H, W, R, iters, lambda0, up, down, all_params, all_before,
-                       all_after, all_accepted, region, stream);
+  rc = lm_refine_chain(all_starts, src, K * B, iters, lambda0, up, down, all_params, all_before, all_after,
+                       all_accepted, region, stream);
   if (rc != SQR_OK) return rc;
-  if (!scored) return sqr_lsq_select(B, K, all_params, all_after, params_out, energy_out, index_out, stream);
-  rc = launch_free_space(st, all_params, target, K * B, B, H, W, R, margin, all_fs, all_after, w_fs, all_score,
-                         (double*)region);
-  if (rc != SQR_OK) return rc;
-  // the winning score goes to energy_out first; the gather puts the winner's point energy there
-  rc = sqr_lsq_select(B, K, all_params, all_score, params_out, energy_out, index_out, stream);
-  if (rc != SQR_OK) return rc;
-  hipLaunchKernelGGL(lsq_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, index_out, all_after, all_fs,
-                     energy_out, energy_fs_out);
-  SQR_HIP_LAUNCH_CHECK("lsq_gather_kernel");
-  return SQR_OK;
+  if constexpr (std::is_same<Src, ImageSrc>::value) {
+    if (fs) {
+      rc = launch_free_space(st, all_params, src.target, K * B, B, src.H, src.W, src.R, fs->margin, fs->all_fs,
+                             all_after, fs->w_fs, fs->all_score, (double*)region);
+      if (rc != SQR_OK) return rc;
+      // the winning score goes to energy_out first; the gather puts the winner's point energy there
+      rc = sqr_lsq_select(B, K, all_params, fs->all_score, params_out, energy_out, index_out, stream);
+      if (rc != SQR_OK) return rc;
+      hipLaunchKernelGGL(lsq_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, index_out, all_after, fs->all_fs,
+                         energy_out, fs->energy_fs_out);
+      SQR_HIP_LAUNCH_CHECK("lsq_gather_kernel");
+      return SQR_OK;
+    }
+  }
+  return sqr_lsq_select(B, K, all_params, all_after, params_out, energy_out, index_out, stream);
 }
 
 extern "C" int sqr_lsq_recover(const float* target, int B, int H, int W, int R, int iters, float e0, double lambda0,
@@ -1047,9 +1169,23 @@ extern "C" int sqr_lsq_recover(const float* target, int B, int H, int W, int R, 
                                void* workspace, size_t workspace_bytes, void* stream) {
   // 3 B samples in one chain: gridDim.y of its launches
   SQR_CHECK_ARG(B >= 1 && 3LL * B <= 65535, "lsq_recover: K=3 x B=%d out of range [1,65535]", B);
-  return recover_chain("lsq_recover", false, target, B, H, W, R, iters, 3, e0, 0.f, nullptr, 0, lambda0, up, down, 0.0,
-                       0.f, params_out, energy_out, nullptr, index_out, nullptr, all_params, all_before, all_after,
-                       nullptr, nullptr, all_accepted, workspace, workspace_bytes, stream);
+  return recover_chain("lsq_recover", nullptr, ImageSrc{target, B, H, W, R}, B, iters, 3, e0, 0.f, nullptr, 0, lambda0,
+                       up, down, params_out, energy_out, index_out, nullptr, all_params, all_before, all_after,
+                       all_accepted, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sqr_pts_recover(const float* points, const int* count, int B, int P, int iters, float e0,
+                               const float* extra, int Kx, double lambda0, double up, double down, float* params_out,
+                               double* energy_out, int* index_out, float* all_starts, float* all_params,
+                               double* all_before, double* all_after, int* all_accepted, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(Kx >= 0 && (Kx == 0 || extra), "pts_recover: Kx=%d extra starts without a pointer", Kx);
+  const long long K = 3LL + Kx;
+  SQR_CHECK_ARG(B >= 1 && K * B <= 65535, "pts_recover: K=%lld x B=%d out of range [1,65535]", K, B);
+  SQR_CHECK_ARG(all_starts, "pts_recover: null pointer");
+  return recover_chain("pts_recover", nullptr, ListSrc{points, count, B, P}, B, iters, 3, e0, 0.f, extra, Kx, lambda0,
+                       up, down, params_out, energy_out, index_out, all_starts, all_params, all_before, all_after,
+                       all_accepted, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sqr_lsq_recover_multi(const float* target, int B, int H, int W, int R, int iters, int nstarts, float e0,
@@ -1062,8 +1198,9 @@ extern "C" int sqr_lsq_recover_multi(const float* target, int B, int H, int W, i
   SQR_CHECK_ARG(Kx >= 0 && (Kx == 0 || extra), "lsq_recover_multi: Kx=%d extra starts without a pointer", Kx);
   const long long K = (long long)nstarts + Kx;
   SQR_CHECK_ARG(B >= 1 && K * B <= 65535, "lsq_recover_multi: K=%lld x B=%d out of range [1,65535]", K, B);
-  return recover_chain("lsq_recover_multi", true, target, B, H, W, R, iters, nstarts, e0, depth, extra, Kx, lambda0, up,
-                       down, w_fs, margin, params_out, energy_out, energy_fs_out, index_out, all_starts, all_params,
-                       all_before, all_after, all_fs, all_score, all_accepted, workspace, workspace_bytes, stream);
+  const FreeSpaceSel fs{w_fs, margin, energy_fs_out, all_fs, all_score};
+  return recover_chain("lsq_recover_multi", &fs, ImageSrc{target, B, H, W, R}, B, iters, nstarts, e0, depth, extra, Kx,
+                       lambda0, up, down, params_out, energy_out, index_out, all_starts, all_params, all_before,
+                       all_after, all_accepted, workspace, workspace_bytes, stream);
 }
 

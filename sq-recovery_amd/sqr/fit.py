@@ -13,10 +13,15 @@ launches on the [B,12] tensor; LM: sqr_lsq_lm_refine, one chain of normal-equati
 recover: the starts' four launches, one such chain over every start of every image and a selection,
 sqr_lsq_recover on the lowest energy of three starts, sqr_lsq_recover_multi on a score with a free-space
 evaluation, from three or six starts and the caller's); nothing is read back inside the loop.
+
+refine_points and recover_points are refine_lm and recover on point lists [B,P,3] (losses.pack_points) instead
+of depth images: the same kernels with a second point source (sqr_pts_lm_refine, sqr_pts_recover).  A cloud
+need not show one side of a body only, and it need not come from this dataset.
 """
 import torch
 
-from .losses import least_squares, lm_refine, lsq_recover, lsq_recover_multi, lsq_starts
+from .losses import (least_squares, lm_refine, lsq_recover, lsq_recover_multi, lsq_starts, pts_lm_refine,
+                     pts_recover, pts_starts)
 
 
 def refine_lm(images, params, iters=10, render_size=32, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
@@ -113,3 +118,83 @@ def refine(images, params, steps=200, lr=2e-3, render_size=32, betas=(0.9, 0.999
     p = p.detach()
     after = least_squares(images, p, R, per_sample=True) if steps else before
     return p, before, after
+
+
+def normalize_points(points, count=None):
+    """points [B,P,3], count [B] or None (any device, plain torch ops, no host wait) -> (points' [B,P,3] f32,
+    scale [B] f32, offset [B,3] f32): every cloud moved into the unit cube, where the parameter clamps live.
+
+    Per cloud, over its counting slots (slot i < count, clamped into [0, P], with three finite coordinates):
+    lo, hi = the coordinatewise minimum and maximum, c = (lo + hi) / 2, s = 0.4 / max(hi - lo), and
+    p' = (p - c) s + 0.5, all in float32.  0.4 puts the sizes where the labels' a <= 0.294 live and leaves t
+    room inside [0,1].  A cloud without counting slots, or whose largest side is zero (or not finite), gets
+    s = 1 and c = 0.5, so p' = p.  Slots that do not count come out as NaN.  scale = s, offset = c."""
+    p = points.detach().to(torch.float32)
+    B, P = p.shape[0], p.shape[1]
+    on = torch.isfinite(p).all(dim=2)
+    if count is not None:
+        n = count.to(device=p.device, dtype=torch.int64).clamp(0, P)
+        on = on & (torch.arange(P, device=p.device)[None, :] < n[:, None])
+    inf = torch.full_like(p, float("inf"))
+    lo = torch.where(on[:, :, None], p, inf).amin(dim=1)
+    hi = torch.where(on[:, :, None], p, -inf).amax(dim=1)
+    side = (hi - lo).amax(dim=1)
+    ok = on.any(dim=1) & (side > 0) & torch.isfinite(side)
+    scale = torch.where(ok, 0.4 / torch.where(ok, side, torch.ones_like(side)), torch.ones_like(side))
+    offset = torch.where(ok[:, None], (lo + hi) / 2, torch.full_like(lo, 0.5))
+    out = (p - offset[:, None, :]) * scale[:, None, None] + 0.5
+    return torch.where(on[:, :, None], out, torch.full_like(out, float("nan"))), scale, offset
+
+
+def denormalize_params(params, scale, offset):
+    """Parameters [...,B,12] fitted to normalize_points' clouds, back in the clouds' own units (float32):
+    a = a' / s, t = (t' - 0.5) / s + c; e and q unchanged."""
+    p = params.to(torch.float32)
+    s = scale.to(torch.float32)[:, None]
+    return torch.cat([p[..., 0:3] / s, p[..., 3:5], (p[..., 5:8] - 0.5) / s + offset.to(torch.float32),
+                      p[..., 8:12]], dim=-1)
+
+
+def refine_points(points, params, count=None, iters=10, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
+    """points [B,P,3] (count [B] or None: losses.pack_points), params [B,12] or [K,B,12] (CUDA) -> (refined f32,
+    energy_before f64, energy_after f64) in params' leading shape, with return_info also the accepted step counts.
+    refine_lm's iteration with the cloud's counting slots as the points; one chain of launches over all samples,
+    no host wait."""
+    out = pts_lm_refine(points, count, params, int(iters), lambda0, up, down)
+    if params.dim() == 2:
+        out = tuple(x[0] for x in out)
+    return out if return_info else out[:3]
+
+
+def recover_points(points, count=None, iters=30, e0=1.0, lambda0=1e-3, up=10.0, down=0.1, extra_starts=None,
+                   normalize=False, return_info=False):
+    """points [B,P,3] (count [B] or None: losses.pack_points; CUDA) -> (params [B,12] f32, energy [B] f64,
+    start_index [B] i32), with return_info also a dict: params [K,B,12], energy_before [K,B], energy_after [K,B],
+    accepted [K,B] of every start, the starts [K,B,12] and the moments (count, centroid, eigenvalues, frame).
+
+    recover on point lists: Solina & Bajcsy's three starts from the cloud's moments and extents, extra_starts
+    ([B,12] or [Kx,B,12]) behind them, one Levenberg-Marquardt chain over all K B samples (K B <= 65535), the
+    lowest energy wins (sqr_pts_recover).  The depth-aware starts and the free-space energy are not offered: a
+    list has no viewpoint.  A cloud without counting slots returns the default start with energy 0.  No host
+    wait, so the call can be captured in a HIP graph.
+
+    The parameter clamps assume a body inside the unit cube.  normalize=True fits normalize_points' clouds
+    instead and returns the parameters in the clouds' own units (denormalize_params; they then need not lie
+    inside the clamps); the energy is that of the normalised fit, extra_starts are taken in normalised units,
+    and info also holds normalized_params [B,12], scale [B] and offset [B,3].
+
+    return_info costs a second run of the starts for the moments, as in recover."""
+    scale = offset = None
+    if normalize:
+        points, scale, offset = normalize_points(points, count)
+    out, energy, index, info = pts_recover(points, count, int(iters), e0, extra_starts, lambda0, up, down)
+    fitted = out
+    if normalize:
+        out = denormalize_params(fitted, scale, offset)
+    if not return_info:
+        return out, energy, index
+    _, moments = pts_starts(points, count, e0)
+    info = dict(moments, **info)
+    if normalize:
+        info.update(normalized_params=fitted, scale=scale, offset=offset)
+    return out, energy, index, info

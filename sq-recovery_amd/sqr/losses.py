@@ -380,6 +380,169 @@ def lsq_recover_multi(target, R, iters, nstarts, e0, depth, extra, lambda0, up, 
     return out, energy, fs, index, info
 
 
+# ---------------------------------------------------------------------------- point lists (sqr_pts_*)
+def pack_points(clouds, device=None):
+    """A list of [N_i,3] clouds (tensors or arrays), or one [B,P,3] batch -> (points [B,P,3] f32 on `device`,
+    count [B] i32): the layout of the sqr_pts_* calls.  P = the longest cloud (at least 1); the slots behind a
+    cloud's own points are NaN, which never counts.  The lengths come from the shapes, so nothing waits for the
+    device.  A [B,P,3] batch is passed through (float32, contiguous) with count = P for every cloud."""
+    if isinstance(clouds, torch.Tensor) or hasattr(clouds, "ndim"):
+        t = torch.as_tensor(clouds)
+        if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError("points must be [B,P,3] with B,P >= 1, got %s" % (tuple(t.shape),))
+        dev = t.device if device is None else torch.device(device)
+        pts = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return pts, torch.full((pts.shape[0],), pts.shape[1], dtype=torch.int32, device=dev)
+    cl = [torch.as_tensor(c) for c in clouds]
+    if not cl:
+        raise ValueError("pack_points: no cloud")
+    for c in cl:
+        if c.dim() != 2 or c.shape[1] != 3:
+            raise ValueError("every cloud must be [N,3], got %s" % (tuple(c.shape),))
+    dev = cl[0].device if device is None else torch.device(device)
+    lens = [int(c.shape[0]) for c in cl]
+    pts = torch.full((len(cl), max(max(lens), 1), 3), float("nan"), dtype=torch.float32, device=dev)
+    for i, c in enumerate(cl):
+        if lens[i]:
+            pts[i, :lens[i]] = c.detach().to(device=dev, dtype=torch.float32)
+    return pts, torch.tensor(lens, dtype=torch.int32).to(dev)
+
+
+def _point_list(points, count):
+    """Checked (points [B,P,3] f32 contiguous, count [B] i32 contiguous or None, B, P) of a CUDA point list."""
+    _require_cuda(points)
+    if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] < 1 or points.shape[1] < 1:
+        raise ValueError("points must be [B,P,3] with B,P >= 1, got %s" % (tuple(points.shape),))
+    pts = points.detach().to(torch.float32).contiguous()
+    B, P = int(pts.shape[0]), int(pts.shape[1])
+    cnt = None
+    if count is not None:
+        _require_cuda(count)
+        if count.dim() != 1 or count.shape[0] != B or count.dtype.is_floating_point:
+            raise ValueError("count must be [%d] integers, got %s %s" % (B, tuple(count.shape), count.dtype))
+        if count.device != pts.device:
+            raise ValueError("points and count are on different devices")
+        cnt = count.detach().to(torch.int32).contiguous()
+    return pts, cnt, B, P
+
+
+def _list_params(params, B, pts):
+    """[S,12] CUDA parameters, S a multiple of the B clouds, as contiguous float32 on the clouds' device."""
+    _require_cuda(params)
+    if params.dim() != 2 or params.shape[1] != 12 or params.shape[0] < B or params.shape[0] % B:
+        raise ValueError("params must be [S,12] with S a multiple of the %d clouds, got %s" % (B, tuple(params.shape)))
+    if params.device != pts.device:
+        raise ValueError("points and params are on different devices")
+    return params.detach().to(torch.float32).contiguous()
+
+
+def point_normal_eq(points, params, count=None):
+    """sqr_pts_normal_eq -> (H [S,12,12], g [S,12], E [S]) float64, no autograd: least_squares_normal_eq on the
+    point list points [B,P,3] (count [B] or None: see pack_points) instead of an image's points.  params [S,12],
+    S a multiple of B, sample s on cloud s mod B.  Two launches, no host wait."""
+    pts, cnt, B, P = _point_list(points, count)
+    p = _list_params(params, B, pts)
+    S, dev = int(p.shape[0]), p.device
+    JtJ = torch.empty(S, 12, 12, dtype=torch.float64, device=dev)
+    Jtr = torch.empty(S, 12, dtype=torch.float64, device=dev)
+    E = torch.empty(S, dtype=torch.float64, device=dev)
+    L = lib()
+    wsb = L.sqr_pts_normal_eq_workspace_bytes(S, P)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_normal_eq(ptr(p), ptr(pts), ptr(cnt), S, B, P, ptr(JtJ), ptr(Jtr), ptr(E), ptr(ws), wsb,
+                              stream_ptr(dev)), "sqr_pts_normal_eq")
+    return JtJ, Jtr, E
+
+
+class PointEnergyFn(torch.autograd.Function):
+    """E_s = a0 a1 a2 sum_points (F_s(point) - 1)^2 over a point list: the normal equations' energy, and
+    dE_s / d params_s = 2 Jtr_s from the same evaluation (no second kernel)."""
+
+    @staticmethod
+    def forward(ctx, points, params, count, per_sample):
+        _, Jtr, E = point_normal_eq(points, params, count)
+        ctx.save_for_backward(Jtr)
+        ctx.params_dtype = params.dtype
+        ctx.is_per_sample = per_sample
+        return E if per_sample else E.mean()
+
+    @staticmethod
+    def backward(ctx, gout):
+        (Jtr,) = ctx.saved_tensors
+        g = gout.to(torch.float64)
+        g = g.unsqueeze(1) if ctx.is_per_sample else g / Jtr.shape[0]
+        return None, (2.0 * Jtr * g).to(torch.float32).to(ctx.params_dtype), None, None
+
+
+def point_energy(points, params, count=None, per_sample=False):
+    """The LeastSquares energy of params [S,12] on the point list points [B,P,3] (count [B] or None), sample s on
+    cloud s mod B: the batch mean as a float64 scalar or, per_sample, the [S] energies; bitwise
+    point_normal_eq's E.  Differentiable w.r.t. params: the gradient is 2 Jtr in float64, times the upstream
+    gradient, rounded to float32 once.  No host wait."""
+    return PointEnergyFn.apply(points, params, count, bool(per_sample))
+
+
+def pts_lm_refine(points, count, params, iters, lambda0, up, down):
+    """sqr_pts_lm_refine: params [K,B,12] (or [B,12] = one slice) -> (params [K,B,12] f32, energy_before [K,B]
+    f64, energy_after [K,B] f64, accepted [K,B] i32).  One chain of launches on the current stream; no host wait."""
+    pts, cnt, B, P = _point_list(points, count)
+    p = _stacked_params(params, B, "params")
+    K, dev = int(p.shape[0]), pts.device
+    out = torch.empty(K, B, 12, dtype=torch.float32, device=dev)
+    before = torch.empty(K, B, dtype=torch.float64, device=dev)
+    after = torch.empty(K, B, dtype=torch.float64, device=dev)
+    accepted = torch.empty(K, B, dtype=torch.int32, device=dev)
+    L = lib()
+    wsb = L.sqr_pts_lm_refine_workspace_bytes(K * B, P)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_lm_refine(ptr(p), ptr(pts), ptr(cnt), K, B, P, int(iters), float(lambda0), float(up), float(down),
+                              ptr(out), ptr(before), ptr(after), ptr(accepted), ptr(ws), wsb, stream_ptr(dev)),
+          "sqr_pts_lm_refine")
+    return out, before, after, accepted
+
+
+def pts_starts(points, count=None, e0=1.0):
+    """sqr_pts_starts -> (starts [3,B,12] f32, info as lsq_starts; info["count"] = the slots that count)."""
+    pts, cnt, B, P = _point_list(points, count)
+    dev = pts.device
+    starts = torch.empty(3, B, 12, dtype=torch.float32, device=dev)
+    info = _moments_info(B, dev)
+    L = lib()
+    wsb = L.sqr_pts_starts_workspace_bytes(B, P)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_starts(ptr(pts), ptr(cnt), B, P, float(e0), ptr(starts), ptr(info["count"]),
+                           ptr(info["centroid"]), ptr(info["eigenvalues"]), ptr(info["frame"]), ptr(ws), wsb,
+                           stream_ptr(dev)), "sqr_pts_starts")
+    return starts, info
+
+
+def pts_recover(points, count, iters, e0, extra, lambda0, up, down):
+    """sqr_pts_recover -> (params [B,12] f32, energy [B] f64, index [B] i32, info dict: starts, params [K,B,12]
+    f32, energy_before, energy_after [K,B] f64, accepted [K,B] i32), K = 3 + the extra starts ([Kx,B,12] or
+    [B,12] or None).  One chain of launches on the current stream; no host wait."""
+    pts, cnt, B, P = _point_list(points, count)
+    dev = pts.device
+    x = _stacked_params(extra, B, "extra_starts") if extra is not None else None
+    Kx = int(x.shape[0]) if x is not None else 0
+    K = 3 + Kx
+    f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)  # noqa: E731
+    out = torch.empty(B, 12, dtype=torch.float32, device=dev)
+    energy = f64(B)
+    index = torch.empty(B, dtype=torch.int32, device=dev)
+    info = {"starts": torch.empty(K, B, 12, dtype=torch.float32, device=dev),
+            "params": torch.empty(K, B, 12, dtype=torch.float32, device=dev),
+            "energy_before": f64(K, B), "energy_after": f64(K, B),
+            "accepted": torch.empty(K, B, dtype=torch.int32, device=dev)}
+    L = lib()
+    wsb = L.sqr_pts_recover_workspace_bytes(K, B, P)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_recover(ptr(pts), ptr(cnt), B, P, int(iters), float(e0), ptr(x), Kx, float(lambda0), float(up),
+                            float(down), ptr(out), ptr(energy), ptr(index), ptr(info["starts"]), ptr(info["params"]),
+                            ptr(info["energy_before"]), ptr(info["energy_after"]), ptr(info["accepted"]), ptr(ws),
+                            wsb, stream_ptr(dev)), "sqr_pts_recover")
+    return out, energy, index, info
+
+
 def implicit_render(params, R, tau=1.0, sharpness=100.0):
     """depth_projection (classes.py:232-282) -> [B,R,R] float32 images (no autograd)."""
     _require_cuda(params)

@@ -39,7 +39,14 @@ produce different images) and to the float64 host renderer on 16 threads over 16
 times sqr.data.OnlineSource.next() (sampler, advance, scanner render) at B = 64, size 256, eagerly and inside
 a replayed graph, next to scan_render alone on the same labels and to the sampler + advance alone, in the
 same process; the difference of the first two is the cost of drawing the labels on the device.  It measures
-everything twice and prints one JSON line per pass."""
+everything twice and prints one JSON line per pass.
+
+    python tools/loss_time.py points
+
+times the point-list stack at B = 64, P = 4096 (the slots of the recover mode's R = 64 scanner-style images, as a
+list in pixel order), 30 iterations: sqr.fit.recover_points next to sqr.fit.recover on the same images, eagerly and
+inside a replayed graph, and losses.point_energy forward + backward next to LeastSquares.energy_function (plain
+torch, forward + backward) on the same CUDA point lists.  Everything twice in one process, one JSON line per pass."""
 import json
 import os
 import sys
@@ -259,12 +266,56 @@ def online(dev, S=256, B=64):
     return res
 
 
+def points(dev, R=64, H=256, B=64, iters=30):
+    """recover_points on the images' slots as lists [B,R^2,3] (NaN where a pixel is not > 0) next to recover on the
+    images, and point_energy next to the plain-torch energy on the same points (there as ragged [3,N_i] lists,
+    built outside the timed region)."""
+    from sqr import fit
+    p = torch.tensor(classes.sample_sq_params(np.random.default_rng(0), B), device=dev)
+    img = losses.scan_render(p, H, 255).unsqueeze(1).contiguous()
+    z = torch.nn.functional.interpolate(img, size=(R, R), mode="nearest")[:, 0]
+    rows, cols = torch.meshgrid(torch.arange(R, device=dev), torch.arange(R, device=dev), indexing="ij")
+    lst = torch.stack([(cols.float() / R).expand_as(z), (1 - rows.float() / R).expand_as(z), z], dim=-1)
+    lst = torch.where((z > 0)[..., None], lst, torch.full_like(lst, float("nan"))).reshape(B, R * R, 3).contiguous()
+    crit = classes.LeastSquares(R, dev)
+    ragged = crit.batch_points(img)
+    torch.manual_seed(0)
+    pred = (p + 0.02 * torch.randn_like(p)).requires_grad_(True)
+
+    def kernel_energy():
+        pred.grad = None
+        losses.point_energy(lst, pred).backward()
+
+    def torch_energy():
+        pred.grad = None
+        crit.energy_function(ragged, pred).mean().backward()
+
+    a = fit.recover(img, iters=iters, render_size=R)
+    b = fit.recover_points(lst, iters=iters)
+    res = {"shape": "P%d_B%d" % (R * R, B), "iters": iters,
+           "points_per_cloud": round(float((z > 0).sum()) / B, 1),
+           "list_equals_image_bitwise": all(torch.equal(x, y) for x, y in zip(a, b)),
+           "recover_eager_ms": round(_eager_ms(lambda: fit.recover(img, iters=iters, render_size=R)), 4),
+           "recover_points_eager_ms": round(_eager_ms(lambda: fit.recover_points(lst, iters=iters)), 4),
+           "recover_in_graph_us": round(_graph_us(lambda: fit.recover(img, iters=iters, render_size=R)), 2),
+           "recover_points_in_graph_us": round(_graph_us(lambda: fit.recover_points(lst, iters=iters)), 2),
+           "point_energy_fwd_bwd_eager_ms": round(_eager_ms(kernel_energy), 4),
+           "torch_energy_fwd_bwd_eager_ms": round(_eager_ms(torch_energy), 4)}
+    res["recover_points_over_recover_in_graph"] = round(res["recover_points_in_graph_us"] / res["recover_in_graph_us"], 4)
+    return res
+
+
 def main():
     dev = torch.device("cuda", 0)
     out = {"env": {k: v for k, v in os.environ.items() if k.startswith("SQR_")}}
     if sys.argv[1:] == ["online"]:
         for _ in range(2):  # every figure twice in one process: one JSON line per pass
             out["online"] = online(dev)
+            print(json.dumps(out))
+        return
+    if sys.argv[1:] == ["points"]:
+        for _ in range(2):  # every figure twice in one process: one JSON line per pass
+            out["points"] = points(dev)
             print(json.dumps(out))
         return
     if sys.argv[1:] == ["scan"]:
