@@ -15,13 +15,14 @@ from . import gradbuf
 from ._lib import SqrTailDesc, SqrTailGrads, check, lib, ptr, stream_ptr
 
 _HEAD_N = (3, 2, 3, 4)
+_DTYPE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # SQR_DTYPE_* of the activation
 
 
 def _desc(x, w0, b0, w1, b1, heads):
     B, C0, H, W = x.shape
     d = SqrTailDesc()
     d.B, d.P, d.C0, d.F1, d.F2 = B, H * W, C0, w0.shape[0], w1.shape[0]
-    d.dtype = {torch.bfloat16: 1, torch.float16: 2}.get(x.dtype, 0)
+    d.dtype = _DTYPE[x.dtype]
     d.w0, d.b0, d.w1, d.b1 = w0.data_ptr(), b0.data_ptr(), w1.data_ptr(), b1.data_ptr()
     for i in range(4):
         d.wh[i] = heads[2 * i].data_ptr()
@@ -146,6 +147,8 @@ def resnet_tail(x, fc, heads):
     """(a, e, t, q) = heads(fc(avgpool(x))) for the NHWC layer-4 activation x [B, C0, H, W]."""
     if not x.is_cuda:
         raise ValueError("sqr tail runs on MI355X; got a %s tensor" % x.device)
+    if x.dtype not in _DTYPE:  # (the kernels would read any other type's bytes as float32)
+        raise ValueError("sqr tail: the activation must be float32, bfloat16 or float16; got %s" % x.dtype)
     hp = []
     for h in heads:
         hp += [h.out_layer[0].weight, h.out_layer[0].bias]

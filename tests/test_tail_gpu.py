@@ -1,7 +1,7 @@
 """Fused ResNetSQ tail (libsqr sqr_tail_*: avgpool + encoder.fc + 4 heads, torch/models.py:186-204)
 vs the same modules in stock torch on the CPU in float64: forward outputs and every gradient.
 fp32 kernel -> tolerance 1e-5 relative to max|ref| (f32 accumulation over <= 512 terms);
-bf16 activations: the input/dx are bf16 (dx compared at bf16 resolution, 1e-2)."""
+bf16 / f16 activations: the input/dx are 16-bit (dx compared at bf16 resolution, 1e-2)."""
 import pytest
 import torch
 import torch.nn as nn
@@ -24,8 +24,9 @@ def _modules(fcn, seed):
     return fc, heads
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("B,H,fcn", [(64, 8, 256), (3, 8, 256), (5, 16, 128), (2, 1, 64)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=["f32", "bf16", "f16"])
+@pytest.mark.parametrize("B,H,fcn", [(64, 8, 256), (3, 8, 256), (5, 16, 128), (2, 1, 64),
+                                     (3, 8, 100), (2, 2, 36)])  # fcn % 16 != 0: the one-launch forward
 @pytest.mark.parametrize("drop", [None, 1], ids=["all_grads", "no_grad_e"])
 def test_tail_matches_torch(B, H, fcn, dtype, drop):
     from sqr import tail
@@ -33,8 +34,8 @@ def test_tail_matches_torch(B, H, fcn, dtype, drop):
     fc, heads = _modules(fcn, B + H)
     g = torch.Generator().manual_seed(7)
     x = torch.randn(B, 512, H, H, generator=g).relu()
-    if dtype == torch.bfloat16:
-        x = x.bfloat16().float()
+    if dtype != torch.float32:
+        x = x.to(dtype).float()
     G = [torch.randn(B, n, generator=g) for n in (3, 2, 3, 4)]
     # reference: the reference's own module graph in float64 on the CPU
     fcr, hr = copy.deepcopy(fc).double(), [copy.deepcopy(h).double() for h in heads]
