@@ -36,7 +36,9 @@
  *   sqr_pts_normal_eq, sqr_pts_lm_refine, sqr_pts_starts, sqr_pts_recover
  *                              the same stack on point lists [B,P,3] (LeastSquares.energy_function's own input,
  *                              classes.py:318-356) instead of depth images
- *   sqr_iou_counts             torch/classes.py:374-447  IoUAccuracy (ins_outs :394-426, __call__ :428-447)
+ *   sqr_pts_seed, sqr_pts_assign, sqr_pts_labeled_lm_refine, sqr_pts_labeled_recover, sqr_pts_recover_parts
+ *                              no counterpart: several superquadrics per point list by assign-and-refit
+ *   sqr_iou_counts            torch/classes.py:374-447  IoUAccuracy (ins_outs :394-426, __call__ :428-447)
  *   sqr_conv2d_fwd / _bwd_data / _bwd_weight
  *                              torch.nn.Conv2d as used by torchvision resnet18 inside ResNetSQ
  *                              (torch/models.py:181-184) and by GenericNetSQ (torch/models.py:134-152)
@@ -414,6 +416,94 @@ int sqr_pts_recover(const float* points, const int* count, int B, int P, int ite
                     int Kx, double lambda0, double up, double down, float* params_out, double* energy_out,
                     int* index_out, float* all_starts, float* all_params, double* all_before, double* all_after,
                     int* all_accepted, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Several superquadrics per point list (assign and refit): a cloud of M bodies is fitted by alternating
+ * "which part explains this point" with "refit every part" (Leonardis, Jaklic, Solina).  B lists as above, M parts
+ * each: 1 <= M <= 16, 3 B M <= 65535 (a recovery's three starts of every part are one chain), 1 <= P <= 2^20.
+ *
+ * Labels are label [B,P] i32: the part of slot i of cloud b, -1 for a slot that does not count (the rule above).
+ * Part (b, m) is the virtual cloud b M + m: the slots of cloud b whose label is m, at their own positions (no copy,
+ * no compaction), so the sqr_pts_labeled_* calls return for it bitwise what their sqr_pts_* counterparts return for
+ * cloud b with every slot of another label set to NaN.  A label outside [0, M) belongs to no part.  The price is
+ * that a part's launch walks all P slots: fitting M parts costs M times one cloud.
+ *
+ * Radial distance of point p to parameters (a, e, t, q): d = |p - t| |1 - f^(-1/2)|, f = F^e1 the quantity whose
+ * f - 1 is the LeastSquares residual over sqrt(a0 a1 a2) (the same clamps, the same zero fix): the distance along
+ * the ray from t to where it meets the surface, exact for a sphere, in the cloud's units.  A d that is not finite
+ * counts as +inf, and so does every d of a row with a NaN parameter.  Assign: label = argmin_m d, the lowest m on a tie, 0 when every d is +inf.
+ *
+ * Seeding: squared distances in float32, (dx dx + dy dy) + dz dz, every operation rounded.  Seed 0 is the counting
+ * slot farthest from the cloud's first counting slot, seed k the one whose distance to the nearest earlier seed is
+ * largest (the lowest slot on a tie; a cloud that has run out of distinct points repeats its last seed, and the
+ * duplicates end as empty parts).  The centres start at the seeds' points; then one nearest-centre assignment (the
+ * lowest m on a tie) and `lloyd` times: every centre := the mean of its part's counting points (float64 sums in a
+ * fixed order, rounded to float32; an empty part keeps its centre), assign again.  The labels returned belong to the
+ * centres returned.  A cloud without a counting slot: seeds -1, centres 0, labels -1.
+ *
+ * No floating-point atomics: every sum below is per block, blocks in order.  Every argument is checked before the
+ * first HIP call (SQR_E_INVALID_ARG, also for a short workspace, launches nothing); no host wait, no allocation. */
+
+/* Workspace (bytes, device) needed by sqr_pts_seed. */
+size_t sqr_pts_seed_workspace_bytes(int B, int P, int M);
+
+/* The seeding: label [B,P] i32, centres [B,M,3] f32, seeds [B,M] i32 (slot indices).  lloyd >= 0.
+ * 2 + 3 lloyd launches. */
+int sqr_pts_seed(const float* points, const int* count, int B, int P, int M, int lloyd, int* label, float* centres,
+                 int* seeds, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_pts_assign. */
+size_t sqr_pts_assign_workspace_bytes(int B, int P, int M);
+
+/* The assignment to params [B,M,12]: label [B,P] i32 and dist [B,P] f32 (the winning d; -1 and 0 for a slot that
+ * does not count), part_count [B,M] i32, part_dist [B,M] f64 (the sum of dist over the part).  label_prev [B,P]
+ * (nullable, not `label` itself): changed [B] i32 = the counting slots whose label differs from it (changed may be
+ * NULL, and is not written, without label_prev).  Two launches. */
+int sqr_pts_assign(const float* points, const int* count, const float* params, const int* label_prev, int B, int P,
+                   int M, int* label, float* dist, int* part_count, double* part_dist, int* changed, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_pts_labeled_lm_refine for S = K B M samples. */
+size_t sqr_pts_labeled_lm_refine_workspace_bytes(int S, int P);
+
+/* sqr_pts_lm_refine on the B M parts of labelled lists: params_in [K,B,M,12], every output shaped [K,B,M].
+ * K B M <= 65535. */
+int sqr_pts_labeled_lm_refine(const float* params_in, const float* points, const int* count, const int* label, int K,
+                              int B, int P, int M, int iters, double lambda0, double up, double down, float* params_out,
+                              double* energy_before, double* energy_after, int* accepted, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_pts_labeled_recover for K = 3 + Kx starts of S = B M parts. */
+size_t sqr_pts_labeled_recover_workspace_bytes(int K, int S, int P);
+
+/* sqr_pts_recover on the B M parts of labelled lists: extra [Kx,B,M,12], the winner's outputs shaped [B,M], the
+ * per-start ones [K,B,M].  A part without a point returns the default start with energy 0.  K B M <= 65535. */
+int sqr_pts_labeled_recover(const float* points, const int* count, const int* label, int B, int P, int M, int iters,
+                            float e0, const float* extra, int Kx, double lambda0, double up, double down,
+                            float* params_out, double* energy_out, int* index_out, float* all_starts,
+                            float* all_params, double* all_before, double* all_after, int* all_accepted,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* Workspace (bytes, device) needed by sqr_pts_recover_parts. */
+size_t sqr_pts_recover_parts_workspace_bytes(int B, int P, int M);
+
+/* The whole alternation in one chain of launches.  The first labels are label_in [B,P] (a segmentation to polish;
+ * not label_out itself) or, label_in NULL, sqr_pts_seed's (seeds [B,M] and centres [B,M,3] are then written, and
+ * may be NULL otherwise).  Round 0 is sqr_pts_labeled_recover with iters0 iterations (three starts per part, the
+ * lowest energy), rounds 1 .. rounds-1 are sqr_pts_labeled_lm_refine with `iters` iterations from the current
+ * parameters; after every round sqr_pts_assign with the round's labels as label_prev.
+ *   params_out [B,M,12] f32, label_out [B,P] i32, dist [B,P] f32, part_count [B,M] i32, part_dist [B,M] f64 :
+ *     the last round's parameters and its assignment, so the labels belong to the parameters
+ *   energy_out [B,M] f64 : each part's LeastSquares energy at the end of the last round's fit, on the labels that
+ *     fit used (the ones before the last assignment)
+ *   changed [rounds,B] i32 : per round the counting slots whose label moved
+ * An empty part: the default start with energy 0 in round 0, left where it is (projected) by a refinement; it may
+ * win points back in a later assignment.  1 <= rounds <= 1024; iters0, iters, lloyd >= 0; the rest as
+ * sqr_pts_recover. */
+int sqr_pts_recover_parts(const float* points, const int* count, const int* label_in, int B, int P, int M, int rounds,
+                          int iters0, int iters, int lloyd, float e0, double lambda0, double up, double down,
+                          float* params_out, int* label_out, double* energy_out, float* dist, int* part_count,
+                          double* part_dist, int* changed, int* seeds, float* centres, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 /* IoUAccuracy(R): per-sample voxel counts [B,2] int64 = (|in_true & in_pred|, |in_true | in_pred|),
  * computed in float64 like the reference. */

@@ -2,7 +2,8 @@
 // f64 MFMA, the Levenberg-Marquardt loop, the classical recovery's starts and selection around it
 // (lsq_moments_kernel .. lsq_select_kernel), the free-space energy over every pixel's ray that the scored
 // selection uses (free_space_kernel), and the one chain the recoveries run (recover_chain).  The points come from
-// depth images (sqr_lsq_*, sqr_least_squares_normal_eq) or from point lists (sqr_pts_*): see "point sources".
+// depth images (sqr_lsq_*, sqr_least_squares_normal_eq), from point lists (sqr_pts_*) or from the labelled parts of
+// point lists (sqr_pts_labeled_*, sqr_pts_recover_parts with its assignment and seeding kernels): see "point sources".
 #include "sqr_common.h"
 #include "sqr_sq_dev.h"
 
@@ -114,6 +115,27 @@ struct ListSrc {
     y = py;
     z = pz;
     return true;
+  }
+};
+
+// The parts of labelled point lists: label [B,P] i32 beside a ListSrc's points and count.  Source v = b M + m is part
+// m of cloud b: slot i of it is slot i of cloud b, and counts iff ListSrc counts it and label[b][i] == m.  Nothing
+// is copied or compacted, so slot positions stay and with them the order of every sum: part (b, m) gives bitwise
+// what the list gives for cloud b with every slot of another label set to NaN.  A label outside [0, M) belongs to
+// no part.  The price: a part's launch walks all P slots of its cloud.
+struct PartSrc {
+  const float* points;
+  const int* count;
+  const int* label;
+  int B, P, M;
+  __host__ __device__ int nsrc() const { return B * M; }
+  __host__ __device__ size_t slots() const { return (size_t)P; }
+  __device__ __forceinline__ bool point(int v, int i, float& x, float& y, float& z) const {
+    const int b = v / M, m = v - b * M;
+    if (!ListSrc{points, count, B, P}.point(b, i, x, y, z)) return false;
+    if (label[(size_t)b * P + i] == m) return true;
+    x = y = z = 0.f;
+    return false;
   }
 };
 
@@ -740,6 +762,285 @@ __global__ void __launch_bounds__(64) lsq_gather_kernel(int B, const int* __rest
   out_fs[b] = energy_fs[at];
 }
 
+// -------------------------------------------------------------------------- several parts: assign and seed
+// A cloud of several bodies is fitted by alternating "which part explains this point" (pts_assign_kernel) with
+// "refit every part" (the chains above on a PartSrc).  The assignment's metric is Solina's radial Euclidean distance
+//   d = |p - t| |1 - f^(-1/2)|,  f = F^e1 (f - 1 is lsq_point_row's row[12]: vox_fwd, its clamps and zero fix),
+// the distance along the ray from the part's centre to where that ray meets the surface: exact for a sphere and in
+// the cloud's units, so a small part is not favoured as the volume-weighted residual would favour it.
+// 1 - f^(-1/2) = -(2^(-e1 lF / 2) - 1) is taken with exp2m1: points of a good fit lie where it is all cancellation.
+// A d that is not finite counts as +inf.  The seeding's metric (kCentre) is the squared distance to a centre,
+// (dx dx + dy dy) + dz dz with every operation rounded (no contraction: the host reference repeats it bit for bit).
+constexpr int kMaxParts = 16;
+constexpr int kPartRow = 20;  // a part's row in LDS: ia 3, t 3, M 9, e1, ie1, ie2, r21, NaN flag (radial) or the centre's 3
+
+__device__ __forceinline__ float sqdist_rn(float px, float py, float pz, float cx, float cy, float cz) {
+#pragma clang fp contract(off)
+  const float dx = px - cx, dy = py - cy, dz = pz - cz;
+  const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  const float xy = xx + yy;
+  return xy + zz;
+}
+
+// grid: (blocks_per_cloud, B); one thread per slot, the slot-to-thread map of the kernels above.  rows: the cloud's M
+// parameter rows [B,M,12] (or centres [B,M,3], kCentre), the same for the whole block: threads 0 .. M-1 prepare one
+// each (sq_load) and leave what the loop needs in LDS.  label [B,P] i32 = argmin_m d (a later m must be strictly
+// nearer: the lowest m on a tie, 0 when every d is +inf), -1 for a slot that does not count (ListSrc's rule); dist
+// [B,P] f32 the winning d, 0 where the label is -1.  prev (nullable): the labels before; a counting slot whose label
+// differs from it is counted.  Per block, in order (lanes by DPP or ballot, waves in order):
+//   pdist [B][nblk][M] f64 the sum of dist per part, pcount [B][nblk][M] i32, pchanged [B][nblk] i32
+template <int NT, bool kCentre>
+__global__ void __launch_bounds__(NT) pts_assign_kernel(const float* __restrict__ points, const int* __restrict__ count,
+                                                        int B, int P, int M, const float* __restrict__ rows,
+                                                        const int* __restrict__ prev, int* __restrict__ label,
+                                                        float* __restrict__ dist, double* __restrict__ pdist,
+                                                        int* __restrict__ pcount, int* __restrict__ pchanged) {
+  __shared__ float part[kMaxParts][kPartRow];
+  __shared__ double red_d[NT / 64][kMaxParts];
+  __shared__ int red_n[NT / 64][kMaxParts + 1];
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if ((int)threadIdx.x < M) {
+    float* r = part[threadIdx.x];
+    if constexpr (kCentre) {
+      const float* c = rows + ((size_t)b * M + threadIdx.x) * 3;
+      r[0] = c[0];
+      r[1] = c[1];
+      r[2] = c[2];
+    } else {
+      SQ s;
+      sq_load(rows + ((size_t)b * M + threadIdx.x) * 12, s);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        r[i] = s.ia[i];
+        r[3 + i] = s.t[i];
+      }
+#pragma unroll
+      for (int i = 0; i < 9; ++i) r[6 + i] = s.M[i];
+      r[15] = s.e1;
+      r[16] = s.ie1;
+      r[17] = s.ie2;
+      r[18] = s.r21;
+      // vox_fwd's fmaxf(., FLT_MIN) drops a NaN square, so a NaN size or rotation would still give a finite d
+      // (the host reference's NaN goes through to d): a row with a NaN parameter has no distance
+      const float* raw = rows + ((size_t)b * M + threadIdx.x) * 12;
+      bool nan = false;
+#pragma unroll
+      for (int i = 0; i < 12; ++i) nan = nan || raw[i] != raw[i];
+      r[19] = nan ? 1.f : 0.f;
+    }
+  }
+  __syncthreads();
+  const int i = blockIdx.x * NT + threadIdx.x;
+  float x, y, z;
+  const bool on = ListSrc{points, count, B, P}.point(b, i, x, y, z);
+  int best = 0;
+  float bd = INFINITY;
+  for (int m = 0; m < M; ++m) {
+    const float* r = part[m];
+    float d;
+    if constexpr (kCentre) {
+      d = sqdist_rn(x, y, z, r[0], r[1], r[2]);
+    } else {
+      SQ s;  // the fields vox_fwd reads
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s.ia[k] = r[k];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s.M[k] = r[6 + k];
+      s.e1 = r[15];
+      s.ie1 = r[16];
+      s.ie2 = r[17];
+      s.r21 = r[18];
+      const float dx = x - r[3], dy = y - r[4], dz = z - r[5];
+      Vox f;
+      vox_fwd(s, dx, dy, dz, f);
+      d = sqrtf(fmaf(dx, dx, fmaf(dy, dy, dz * dz))) * fabsf(exp2m1(-0.5f * s.e1 * f.lF));
+      if (r[19] != 0.f) d = INFINITY;
+    }
+    d = d < INFINITY ? d : INFINITY;  // NaN too
+    if (m == 0 || d < bd) {
+      bd = d;
+      best = m;
+    }
+  }
+  const int lab = on ? best : -1;
+  const float dw = on ? bd : 0.f;
+  bool moved = false;
+  if (i < P) {
+    const size_t at = (size_t)b * P + i;
+    label[at] = lab;
+    if (dist) dist[at] = dw;
+    moved = prev && on && prev[at] != lab;
+  }
+  for (int m = 0; m < M; ++m) {  // every lane is active here: wave_sum_d's condition
+    const bool mine = lab == m;
+    const double v = wave_sum_d(mine ? (double)dw : 0.0);
+    const int n = __popcll(__ballot(mine));
+    if (lane == 0) {
+      red_d[wid][m] = v;
+      red_n[wid][m] = n;
+    }
+  }
+  const int nmoved = __popcll(__ballot(moved));
+  if (lane == 0) red_n[wid][kMaxParts] = nmoved;
+  __syncthreads();
+  const size_t blk = (size_t)b * gridDim.x + blockIdx.x;
+  if ((int)threadIdx.x < M) {
+    double v = 0.0;
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) {
+      v += red_d[w][threadIdx.x];
+      n += red_n[w][threadIdx.x];
+    }
+    pdist[blk * M + threadIdx.x] = v;
+    pcount[blk * M + threadIdx.x] = n;
+  }
+  if (threadIdx.x == 0) {
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) n += red_n[w][kMaxParts];
+    pchanged[blk] = n;
+  }
+}
+
+// One thread per part (b, m): the blocks' partials in order.  changed (nullable) [B]: written by the thread of m = 0.
+__global__ void __launch_bounds__(64) pts_assign_finalize_kernel(int B, int M, int nblk,
+                                                                 const double* __restrict__ pdist,
+                                                                 const int* __restrict__ pcount,
+                                                                 const int* __restrict__ pchanged,
+                                                                 int* __restrict__ part_count,
+                                                                 double* __restrict__ part_dist,
+                                                                 int* __restrict__ changed) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= B * M) return;
+  const int b = v / M, m = v - b * M;
+  double d = 0.0;
+  int n = 0;
+  for (int k = 0; k < nblk; ++k) {
+    d += pdist[((size_t)b * nblk + k) * M + m];
+    n += pcount[((size_t)b * nblk + k) * M + m];
+  }
+  part_dist[v] = d;
+  part_count[v] = n;
+  if (m == 0 && changed) {
+    int c = 0;
+    for (int k = 0; k < nblk; ++k) c += pchanged[(size_t)b * nblk + k];
+    changed[b] = c;
+  }
+}
+
+// the farther of two (distance, slot) candidates, the lower slot at equal distance
+__device__ __forceinline__ void far_take(float& v, int& i, float ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) {
+    v = ov;
+    i = oi;
+  }
+}
+
+// Farthest-point seeding, one block per cloud, M passes over its slots (thread t owns the slots t mod NT, so the
+// running minimum mind [B,P] f32 needs no barrier).  Pass 0 measures from the first counting slot and its farthest
+// slot is seed 0; pass k >= 1 folds seed k-1 into mind (pass 1 sets it) and the slot of the largest mind is seed k.
+// A candidate must be strictly farther than the running best, which starts at (distance 0, the slot measured
+// from): the lowest slot wins a tie, and a cloud that has run out of distinct points repeats its last seed.
+// seeds [B,M] i32, centres [B,M,3] f32 = the seeds' points.  No counting slot: seeds -1, centres 0.
+template <int NT>
+__global__ void __launch_bounds__(NT) pts_fps_kernel(const float* __restrict__ points, const int* __restrict__ count,
+                                                     int B, int P, int M, float* __restrict__ mind,
+                                                     int* __restrict__ seeds, float* __restrict__ centres) {
+  __shared__ float rv[2][NT / 64];
+  __shared__ int ri[2][NT / 64];
+  __shared__ int seed_of[kMaxParts];
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const ListSrc src{points, count, B, P};
+  float x, y, z;
+  int first = P;
+  for (int i = threadIdx.x; i < P && first == P; i += NT)
+    if (src.point(b, i, x, y, z)) first = i;
+  for (int o = 32; o >= 1; o >>= 1) first = min(first, __shfl_xor(first, o));
+  if (lane == 0) ri[1][wid] = first;
+  __syncthreads();
+  first = ri[1][0];
+#pragma unroll
+  for (int w = 1; w < NT / 64; ++w) first = min(first, ri[1][w]);
+  if (first == P) {  // the same in every thread
+    if ((int)threadIdx.x < M) {
+      seeds[(size_t)b * M + threadIdx.x] = -1;
+      float* c = centres + ((size_t)b * M + threadIdx.x) * 3;
+      c[0] = c[1] = c[2] = 0.f;
+    }
+    return;
+  }
+  float* md = mind + (size_t)b * P;
+  int from = first;
+  for (int k = 0; k < M; ++k) {
+    // pass k writes buffer k & 1; a wave reaches pass k + 2's write only through pass k + 1's barrier, behind
+    // every wave's reads of pass k
+    const float* c = points + ((size_t)b * P + from) * 3;
+    const float cx = c[0], cy = c[1], cz = c[2];
+    float bv = 0.f;
+    int bi = from;
+    for (int i = threadIdx.x; i < P; i += NT) {
+      if (!src.point(b, i, x, y, z)) continue;
+      float d = sqdist_rn(x, y, z, cx, cy, cz);
+      if (k == 1) md[i] = d;
+      if (k > 1) {
+        d = fminf(md[i], d);
+        md[i] = d;
+      }
+      if (d > bv) {  // ascending slots: the first of equal distances stays
+        bv = d;
+        bi = i;
+      }
+    }
+    for (int o = 32; o >= 1; o >>= 1) far_take(bv, bi, __shfl_xor(bv, o), __shfl_xor(bi, o));
+    if (lane == 0) {
+      rv[k & 1][wid] = bv;
+      ri[k & 1][wid] = bi;
+    }
+    __syncthreads();
+    bv = rv[k & 1][0];
+    bi = ri[k & 1][0];
+#pragma unroll
+    for (int w = 1; w < NT / 64; ++w) far_take(bv, bi, rv[k & 1][w], ri[k & 1][w]);
+    from = bi;
+    if (threadIdx.x == 0) seed_of[k] = bi;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < M) {
+    const int s = seed_of[threadIdx.x];
+    seeds[(size_t)b * M + threadIdx.x] = s;
+    const float* p = points + ((size_t)b * P + s) * 3;
+    float* c = centres + ((size_t)b * M + threadIdx.x) * 3;
+    c[0] = p[0];
+    c[1] = p[1];
+    c[2] = p[2];
+  }
+}
+
+// One thread per part (b, m): its centre := the mean of its counting points, from lsq_moments_kernel's partials on
+// the PartSrc ([B M][nblk][kMomN]: sum x = 3, sum y = 6, sum z = 8, n = 9), blocks in order, float64, rounded to
+// float32 once.  An empty part keeps its centre.
+__global__ void __launch_bounds__(64) pts_centre_kernel(int BM, int nblk, const double* __restrict__ partials,
+                                                        float* __restrict__ centres) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= BM) return;
+  double sx = 0.0, sy = 0.0, sz = 0.0, n = 0.0;
+  for (int k = 0; k < nblk; ++k) {
+    const double* src = partials + ((size_t)v * nblk + k) * kMomN;
+    sx += src[3];
+    sy += src[6];
+    sz += src[8];
+    n += src[9];
+  }
+  if (n > 0.0) {
+    centres[3 * (size_t)v] = (float)(sx / n);
+    centres[3 * (size_t)v + 1] = (float)(sy / n);
+    centres[3 * (size_t)v + 2] = (float)(sz / n);
+  }
+}
+
 }  // namespace sqr
 
 using namespace sqr;
@@ -775,6 +1076,13 @@ static int check_source(const char* who, const ImageSrc& src) {
 static int check_source(const char* who, const ListSrc& src) {
   SQR_CHECK_ARG(src.P >= 1 && src.P <= kMaxListSlots, "%s: P=%d out of range [1,%d]", who, src.P, kMaxListSlots);
   SQR_CHECK_ARG(src.points, "%s: null pointer", who);
+  return SQR_OK;
+}
+
+static int check_source(const char* who, const PartSrc& src) {
+  SQR_CHECK_ARG(src.M >= 1 && src.M <= kMaxParts, "%s: M=%d out of range [1,%d]", who, src.M, kMaxParts);
+  SQR_CHECK_ARG(src.P >= 1 && src.P <= kMaxListSlots, "%s: P=%d out of range [1,%d]", who, src.P, kMaxListSlots);
+  SQR_CHECK_ARG(src.points && src.label, "%s: null pointer", who);
   return SQR_OK;
 }
 
@@ -1204,3 +1512,228 @@ extern "C" int sqr_lsq_recover_multi(const float* target, int B, int H, int W, i
                        all_after, all_accepted, workspace, workspace_bytes, stream);
 }
 
+
+// -------------------------------------------------------------------------- several parts per cloud (C ABI)
+// B clouds of M parts: 3 B M samples are one recovery chain's gridDim.y
+static int check_parts(const char* who, int B, int P, int M) {
+  SQR_CHECK_ARG(M >= 1 && M <= kMaxParts, "%s: M=%d out of range [1,%d]", who, M, kMaxParts);
+  SQR_CHECK_ARG(B >= 1 && 3LL * B * M <= 65535, "%s: 3 x B=%d x M=%d out of range [1,65535]", who, B, M);
+  SQR_CHECK_ARG(P >= 1 && P <= kMaxListSlots, "%s: P=%d out of range [1,%d]", who, P, kMaxListSlots);
+  return SQR_OK;
+}
+
+// the assignment's per-block partials: pdist [B][nblk][M] f64, pcount [B][nblk][M] i32, pchanged [B][nblk] i32
+static size_t assign_bytes(size_t B, size_t P, size_t M) {
+  const size_t n = B * slot_blocks(P);
+  return (n * M * (sizeof(double) + sizeof(int)) + n * sizeof(int) + 7) / 8 * 8;
+}
+
+extern "C" size_t sqr_pts_assign_workspace_bytes(int B, int P, int M) {
+  if (B <= 0 || P <= 0 || M <= 0) return 0;
+  return assign_bytes((size_t)B, (size_t)P, (size_t)M);
+}
+
+// the assignment's launches (arguments checked by the callers); part_count NULL: no finalize (the Lloyd iterations)
+template <bool kCentre>
+static int launch_assign(hipStream_t st, const float* points, const int* count, int B, int P, int M,
+                         const float* rows, const int* prev, int* label, float* dist, int* part_count,
+                         double* part_dist, int* changed, void* workspace) {
+  const int nblk = (int)slot_blocks((size_t)P);
+  double* pdist = (double*)workspace;
+  int* pcount = (int*)(pdist + (size_t)B * nblk * M);
+  int* pchanged = pcount + (size_t)B * nblk * M;
+  hipLaunchKernelGGL((pts_assign_kernel<256, kCentre>), dim3(nblk, B), dim3(256), 0, st, points, count, B, P, M, rows,
+                     prev, label, dist, pdist, pcount, pchanged);
+  SQR_HIP_LAUNCH_CHECK("pts_assign_kernel");
+  if (!part_count) return SQR_OK;
+  hipLaunchKernelGGL(pts_assign_finalize_kernel, dim3((B * M + 63) / 64), dim3(64), 0, st, B, M, nblk, pdist, pcount,
+                     pchanged, part_count, part_dist, prev ? changed : nullptr);
+  SQR_HIP_LAUNCH_CHECK("pts_assign_finalize_kernel");
+  return SQR_OK;
+}
+
+extern "C" int sqr_pts_assign(const float* points, const int* count, const float* params, const int* label_prev,
+                              int B, int P, int M, int* label, float* dist, int* part_count, double* part_dist,
+                              int* changed, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = check_parts("pts_assign", B, P, M);
+  if (rc != SQR_OK) return rc;
+  SQR_CHECK_ARG(points && params && label && dist && part_count && part_dist && workspace && (!label_prev || changed),
+                "pts_assign: null pointer");
+  SQR_CHECK_ARG(label_prev != label, "pts_assign: label and label_prev are the same buffer");
+  const size_t need = assign_bytes((size_t)B, (size_t)P, (size_t)M);
+  SQR_CHECK_ARG(workspace_bytes >= need, "pts_assign: workspace %zu < %zu bytes", workspace_bytes, need);
+  return launch_assign<false>(as_stream(stream), points, count, B, P, M, params, label_prev, label, dist, part_count,
+                              part_dist, changed, workspace);
+}
+
+// The seeding's workspace: mind [B,P] f32 (the Lloyd assignments' dist afterwards), the assignment's partials, the
+// moments' partials [B M][nblk][kMomN] f64
+static size_t seed_bytes(size_t B, size_t P, size_t M) {
+  return (B * P * sizeof(float) + 7) / 8 * 8 + assign_bytes(B, P, M) + B * M * slot_blocks(P) * kMomN * sizeof(double);
+}
+
+extern "C" size_t sqr_pts_seed_workspace_bytes(int B, int P, int M) {
+  if (B <= 0 || P <= 0 || M <= 0) return 0;
+  return seed_bytes((size_t)B, (size_t)P, (size_t)M);
+}
+
+// the seeding's launches (arguments checked by the callers): 2 + 3 lloyd
+static int launch_seed(hipStream_t st, const float* points, const int* count, int B, int P, int M, int lloyd,
+                       int* label, float* centres, int* seeds, void* workspace) {
+  const int nblk = (int)slot_blocks((size_t)P);
+  float* mind = (float*)workspace;
+  char* asg = (char*)workspace + ((size_t)B * P * sizeof(float) + 7) / 8 * 8;
+  double* mom = (double*)(asg + assign_bytes((size_t)B, (size_t)P, (size_t)M));
+  hipLaunchKernelGGL((pts_fps_kernel<256>), dim3(B), dim3(256), 0, st, points, count, B, P, M, mind, seeds, centres);
+  SQR_HIP_LAUNCH_CHECK("pts_fps_kernel");
+  int rc = launch_assign<true>(st, points, count, B, P, M, centres, nullptr, label, mind, nullptr, nullptr, nullptr,
+                               asg);
+  if (rc != SQR_OK) return rc;
+  const PartSrc src{points, count, label, B, P, M};
+  for (int it = 0; it < lloyd; ++it) {
+    hipLaunchKernelGGL((lsq_moments_kernel<256, PartSrc>), dim3(nblk, B * M), dim3(256), 0, st, src, mom);
+    SQR_HIP_LAUNCH_CHECK("lsq_moments_kernel");
+    hipLaunchKernelGGL(pts_centre_kernel, dim3((B * M + 63) / 64), dim3(64), 0, st, B * M, nblk, mom, centres);
+    SQR_HIP_LAUNCH_CHECK("pts_centre_kernel");
+    rc = launch_assign<true>(st, points, count, B, P, M, centres, nullptr, label, mind, nullptr, nullptr, nullptr, asg);
+    if (rc != SQR_OK) return rc;
+  }
+  return SQR_OK;
+}
+
+extern "C" int sqr_pts_seed(const float* points, const int* count, int B, int P, int M, int lloyd, int* label,
+                            float* centres, int* seeds, void* workspace, size_t workspace_bytes, void* stream) {
+  const int rc = check_parts("pts_seed", B, P, M);
+  if (rc != SQR_OK) return rc;
+  SQR_CHECK_ARG(lloyd >= 0, "pts_seed: lloyd=%d must be >= 0", lloyd);
+  SQR_CHECK_ARG(points && label && centres && seeds && workspace, "pts_seed: null pointer");
+  const size_t need = seed_bytes((size_t)B, (size_t)P, (size_t)M);
+  SQR_CHECK_ARG(workspace_bytes >= need, "pts_seed: workspace %zu < %zu bytes", workspace_bytes, need);
+  return launch_seed(as_stream(stream), points, count, B, P, M, lloyd, label, centres, seeds, workspace);
+}
+
+extern "C" size_t sqr_pts_labeled_lm_refine_workspace_bytes(int S, int P) { return sqr_pts_lm_refine_workspace_bytes(S, P); }
+
+extern "C" int sqr_pts_labeled_lm_refine(const float* params_in, const float* points, const int* count,
+                                         const int* label, int K, int B, int P, int M, int iters, double lambda0,
+                                         double up, double down, float* params_out, double* energy_before,
+                                         double* energy_after, int* accepted, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+  SQR_CHECK_ARG(K >= 1 && B >= 1 && M >= 1 && (long long)K * B * M <= 65535,
+                "pts_labeled_lm_refine: K=%d x B=%d x M=%d out of range [1,65535]", K, B, M);
+  return lm_refine_entry("pts_labeled_lm_refine", params_in, PartSrc{points, count, label, B, P, M}, K, B * M, iters,
+                         lambda0, up, down, params_out, energy_before, energy_after, accepted, workspace,
+                         workspace_bytes, stream);
+}
+
+extern "C" size_t sqr_pts_labeled_recover_workspace_bytes(int K, int S, int P) {
+  return sqr_pts_recover_workspace_bytes(K, S, P);
+}
+
+extern "C" int sqr_pts_labeled_recover(const float* points, const int* count, const int* label, int B, int P, int M,
+                                       int iters, float e0, const float* extra, int Kx, double lambda0, double up,
+                                       double down, float* params_out, double* energy_out, int* index_out,
+                                       float* all_starts, float* all_params, double* all_before, double* all_after,
+                                       int* all_accepted, void* workspace, size_t workspace_bytes, void* stream) {
+  SQR_CHECK_ARG(Kx >= 0 && (Kx == 0 || extra), "pts_labeled_recover: Kx=%d extra starts without a pointer", Kx);
+  const long long K = 3LL + Kx;
+  SQR_CHECK_ARG(B >= 1 && M >= 1 && K * B * M <= 65535, "pts_labeled_recover: K=%lld x B=%d x M=%d out of range [1,65535]",
+                K, B, M);
+  SQR_CHECK_ARG(all_starts, "pts_labeled_recover: null pointer");
+  return recover_chain("pts_labeled_recover", nullptr, PartSrc{points, count, label, B, P, M}, B * M, iters, 3, e0, 0.f,
+                       extra, Kx, lambda0, up, down, params_out, energy_out, index_out, all_starts, all_params,
+                       all_before, all_after, all_accepted, workspace, workspace_bytes, stream);
+}
+
+// sqr_pts_recover_parts' workspace over S = B M parts: the second label and parameter buffers (the rounds alternate
+// between them and the outputs), round 0's per-start outputs (all_params [3,S,12] f32, all_before / all_after [3,S]
+// f64, all_accepted [3,S] i32, index [S] i32; the later rounds' energy_before and accepted lie in them), the
+// assignment's partials, and one region that the seeding and the recovery chain (its starts inside) use in turn
+struct PartsLayout {
+  size_t label2, params2, all_before, all_after, all_params, all_accepted, index, assign, region, region_bytes, total;
+};
+
+static PartsLayout parts_layout(size_t B, size_t P, size_t M) {
+  const size_t S = B * M;
+  auto up8 = [](size_t n) { return (n + 7) / 8 * 8; };
+  PartsLayout l;
+  size_t at = 0;
+  l.all_before = at; at += 3 * S * sizeof(double);
+  l.all_after = at;  at += 3 * S * sizeof(double);
+  l.assign = at;     at += assign_bytes(B, P, M);
+  l.region = at;
+  const size_t rec = recover_bytes(3, S, P) + 3 * S * 12 * sizeof(float), sd = seed_bytes(B, P, M);
+  l.region_bytes = up8(rec > sd ? rec : sd);
+  at += l.region_bytes;
+  l.label2 = at;       at += up8(B * P * sizeof(int));
+  l.params2 = at;      at += up8(S * 12 * sizeof(float));
+  l.all_params = at;   at += up8(3 * S * 12 * sizeof(float));
+  l.all_accepted = at; at += up8(3 * S * sizeof(int));
+  l.index = at;        at += up8(S * sizeof(int));
+  l.total = at;
+  return l;
+}
+
+extern "C" size_t sqr_pts_recover_parts_workspace_bytes(int B, int P, int M) {
+  if (B <= 0 || P <= 0 || M <= 0) return 0;
+  return parts_layout((size_t)B, (size_t)P, (size_t)M).total;
+}
+
+extern "C" int sqr_pts_recover_parts(const float* points, const int* count, const int* label_in, int B, int P, int M,
+                                     int rounds, int iters0, int iters, int lloyd, float e0, double lambda0, double up,
+                                     double down, float* params_out, int* label_out, double* energy_out,
+                                     float* dist, int* part_count, double* part_dist, int* changed, int* seeds,
+                                     float* centres, void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = check_parts("pts_recover_parts", B, P, M);
+  if (rc != SQR_OK) return rc;
+  SQR_CHECK_ARG(rounds >= 1 && rounds <= 1024, "pts_recover_parts: rounds=%d out of range [1,1024]", rounds);
+  SQR_CHECK_ARG(iters0 >= 0 && iters >= 0, "pts_recover_parts: iters0=%d, iters=%d must be >= 0", iters0, iters);
+  SQR_CHECK_ARG(lloyd >= 0, "pts_recover_parts: lloyd=%d must be >= 0", lloyd);
+  SQR_CHECK_ARG(e0 >= 0.1f && e0 <= 1.f, "pts_recover_parts: e0=%g outside [0.1,1]", (double)e0);
+  SQR_CHECK_ARG(lambda0 > 0.0, "pts_recover_parts: lambda0=%g must be > 0", lambda0);
+  SQR_CHECK_ARG(up > 1.0, "pts_recover_parts: up=%g must be > 1", up);
+  SQR_CHECK_ARG(down > 0.0 && down < 1.0, "pts_recover_parts: down=%g outside (0,1)", down);
+  SQR_CHECK_ARG(points && params_out && label_out && energy_out && dist && part_count && part_dist && changed &&
+                    workspace && (label_in || (seeds && centres)),
+                "pts_recover_parts: null pointer");
+  SQR_CHECK_ARG(label_in != label_out, "pts_recover_parts: label_in and label_out are the same buffer");
+  const PartsLayout l = parts_layout((size_t)B, (size_t)P, (size_t)M);
+  SQR_CHECK_ARG(workspace_bytes >= l.total, "pts_recover_parts: workspace %zu < %zu bytes", workspace_bytes, l.total);
+  hipStream_t st = as_stream(stream);
+  char* ws = (char*)workspace;
+  const int S = B * M;
+  double* all_before = (double*)(ws + l.all_before);
+  double* all_after = (double*)(ws + l.all_after);
+  float* all_params = (float*)(ws + l.all_params);
+  int* all_accepted = (int*)(ws + l.all_accepted);
+  int* index = (int*)(ws + l.index);
+  // round t writes labels and parameters into buffer (rounds - 1 - t) & 1: 0 the outputs, 1 the workspace's, so
+  // that the last round ends in the outputs and no round reads what it writes
+  int* lbuf[2] = {label_out, (int*)(ws + l.label2)};
+  float* pbuf[2] = {params_out, (float*)(ws + l.params2)};
+  const int* cur = label_in;
+  if (!cur) {
+    int* first = lbuf[rounds & 1];
+    rc = launch_seed(st, points, count, B, P, M, lloyd, first, centres, seeds, ws + l.region);
+    if (rc != SQR_OK) return rc;
+    cur = first;
+  }
+  for (int t = 0; t < rounds; ++t) {
+    const int w = (rounds - 1 - t) & 1;
+    const PartSrc src{points, count, cur, B, P, M};
+    if (t == 0) {
+      rc = recover_chain("pts_recover_parts", nullptr, src, S, iters0, 3, e0, 0.f, nullptr, 0, lambda0, up, down,
+                         pbuf[w], energy_out, index, nullptr, all_params, all_before, all_after, all_accepted,
+                         ws + l.region, l.region_bytes, stream);
+    } else {
+      rc = lm_refine_chain(pbuf[w ^ 1], src, S, iters, lambda0, up, down, pbuf[w], all_before, energy_out,
+                           all_accepted, ws + l.region, stream);
+    }
+    if (rc != SQR_OK) return rc;
+    rc = launch_assign<false>(st, points, count, B, P, M, pbuf[w], cur, lbuf[w], dist, part_count, part_dist,
+                              changed + (size_t)t * B, ws + l.assign);
+    if (rc != SQR_OK) return rc;
+    cur = lbuf[w];
+  }
+  return SQR_OK;
+}

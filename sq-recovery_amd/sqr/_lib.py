@@ -132,6 +132,22 @@ SIGNATURES = {
     "sqr_pts_recover_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sqr_pts_recover": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_double, c_double,
                                 c_double] + [c_void_p] * 9 + [c_size_t, c_void_p]),
+    "sqr_pts_seed_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sqr_pts_seed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_size_t, c_void_p]),
+    "sqr_pts_assign_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sqr_pts_assign": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sqr_pts_labeled_lm_refine_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "sqr_pts_labeled_lm_refine": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                          c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
+    "sqr_pts_labeled_recover_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sqr_pts_labeled_recover": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                        c_int, c_double, c_double, c_double] + [c_void_p] * 9 + [c_size_t, c_void_p]),
+    "sqr_pts_recover_parts_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sqr_pts_recover_parts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_float, c_double, c_double, c_double] + [c_void_p] * 10 + [c_size_t, c_void_p]),
     "sqr_iou_counts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sqr_iou_counts_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sqr_conv2d_out_hw": (c_int, [ctypes.POINTER(SqrConvDesc), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),

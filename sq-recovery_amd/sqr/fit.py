@@ -17,11 +17,15 @@ evaluation, from three or six starts and the caller's); nothing is read back ins
 refine_points and recover_points are refine_lm and recover on point lists [B,P,3] (losses.pack_points) instead
 of depth images: the same kernels with a second point source (sqr_pts_lm_refine, sqr_pts_recover).  A cloud
 need not show one side of a body only, and it need not come from this dataset.
+
+recover_parts fits several superquadrics to one cloud by alternating assign_points (every point to the part whose
+surface is nearest) with a refit of every part, the same kernels once more on a third point source: the slots of
+a cloud that carry a part's label (sqr_pts_recover_parts).
 """
 import torch
 
-from .losses import (least_squares, lm_refine, lsq_recover, lsq_recover_multi, lsq_starts, pts_lm_refine,
-                     pts_recover, pts_starts)
+from .losses import (_parts_shapes, least_squares, lm_refine, lsq_recover, lsq_recover_multi, lsq_starts,
+                     pts_assign, pts_lm_refine, pts_recover, pts_recover_parts, pts_starts)
 
 
 def refine_lm(images, params, iters=10, render_size=32, lambda0=1e-3, up=10.0, down=0.1, return_info=False):
@@ -198,3 +202,47 @@ def recover_points(points, count=None, iters=30, e0=1.0, lambda0=1e-3, up=10.0, 
     if normalize:
         info.update(normalized_params=fitted, scale=scale, offset=offset)
     return out, energy, index, info
+
+
+def assign_points(points, params, count=None):
+    """points [B,P,3] (count [B] or None), params [B,M,12] (CUDA) -> (labels [B,P] i32, dist [B,P] f32): every
+    counting slot's nearest part by the radial distance d = |p - t| |1 - f^(-1/2)| (f = F^e1: the distance along the
+    ray from the part's centre to its surface, in the cloud's units), the lowest part on a tie; -1 and 0 for a slot
+    that does not count (sqr_pts_assign).  Two launches, no host wait."""
+    out = pts_assign(points, params, count)
+    return out["label"], out["dist"]
+
+
+def recover_parts(points, parts, count=None, rounds=3, iters0=30, iters=10, lloyd=10, e0=1.0, lambda0=1e-3, up=10.0,
+                  down=0.1, labels=None, normalize=False, return_info=False):
+    """points [B,P,3] (count [B] or None: losses.pack_points; CUDA), parts = M bodies per cloud -> (params
+    [B,M,12] f32, labels [B,P] i32, energy [B,M] f64), with return_info also a dict: dist [B,P] f32 (every slot's
+    radial distance to its part), part_count [B,M] i32, part_dist [B,M] f64 (the sum of dist per part), changed
+    [rounds,B] i32 (the points whose label moved in each round's assignment) and, when it seeded, seeds [B,M] i32
+    and centres [B,M,3] f32.
+
+    Several superquadrics per cloud by assign-and-refit (Leonardis, Jaklic, Solina): the cloud is split into M
+    parts by farthest-point seeds and `lloyd` Lloyd iterations (or by `labels` [B,P] i32, a segmentation to
+    polish; a label outside [0, M) belongs to no part); round 0 recovers every part as recover_points does (three
+    starts, iters0 iterations, the lowest energy), every later round refines it by `iters` Levenberg-Marquardt
+    iterations from where it is; after every round each point goes to the part whose surface is nearest
+    (assign_points).  The labels returned are the last assignment's, so they belong to the parameters returned;
+    energy is each part's LeastSquares energy at the end of the last fit, on the labels that fit used.  -1 labels
+    the slots that do not count.  An empty part returns the default start with energy 0 and may win points back
+    in a later round.  M is the caller's: nothing here chooses it, and parts that touch are not told apart.
+
+    1 <= parts <= 16 and 3 B parts <= 65535; a part's launch walks its whole cloud, so the fit costs M times one
+    cloud's.  The whole call (sqr_pts_recover_parts) is one chain of launches with no host wait: it can be
+    captured in a HIP graph.  normalize=True as in recover_points: all M parts of a cloud share its scale and
+    offset, energy and dist are those of the normalised cloud, and info also holds normalized_params, scale and
+    offset."""
+    _parts_shapes(points, parts, labels)
+    scale = offset = None
+    if normalize:
+        points, scale, offset = normalize_points(points, count)
+    out, lab, energy, info = pts_recover_parts(points, count, parts, labels, int(rounds), int(iters0), int(iters),
+                                               int(lloyd), e0, lambda0, up, down)
+    if normalize:
+        info.update(normalized_params=out, scale=scale, offset=offset)
+        out = denormalize_params(out.transpose(0, 1), scale, offset).transpose(0, 1).contiguous()
+    return (out, lab, energy, info) if return_info else (out, lab, energy)

@@ -543,6 +543,178 @@ def pts_recover(points, count, iters, e0, extra, lambda0, up, down):
     return out, energy, index, info
 
 
+MAX_PARTS = 16
+
+
+def _parts(B, M):
+    """The checked number of parts per cloud: 1 <= M <= 16 and 3 B M <= 65535 (one recovery chain)."""
+    M = int(M)
+    if not 1 <= M <= MAX_PARTS:
+        raise ValueError("parts must be in [1,%d], got %d" % (MAX_PARTS, M))
+    if 3 * B * M > 65535:
+        raise ValueError("3 x %d clouds x %d parts = %d samples in one chain, more than 65535" % (B, M, 3 * B * M))
+    return M
+
+
+def _parts_shapes(points, parts, labels=None, what="labels"):
+    """What the several-parts calls check on shapes and dtypes alone, before anything asks for a device: points
+    [B,P,3], the number of parts, labels (optional) an int32 tensor [B,P].  -> M."""
+    if points.dim() != 3 or points.shape[2] != 3 or points.shape[0] < 1 or points.shape[1] < 1:
+        raise ValueError("points must be [B,P,3] with B,P >= 1, got %s" % (tuple(points.shape),))
+    B, P = int(points.shape[0]), int(points.shape[1])
+    M = _parts(B, parts)
+    if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32 or
+                               tuple(labels.shape) != (B, P)):
+        raise ValueError("%s must be an int32 tensor [%d,%d], got %s %s" % (
+            what, B, P, tuple(getattr(labels, "shape", ())), getattr(labels, "dtype", type(labels))))
+    return M
+
+
+def _labels(labels, pts, what="labels"):
+    """[B,P] int32 CUDA labels of the point list pts, contiguous."""
+    _parts_shapes(pts, 1, labels, what)
+    _require_cuda(labels)
+    if labels.device != pts.device:
+        raise ValueError("points and %s are on different devices" % what)
+    return labels.detach().contiguous()
+
+
+def _part_params(params, B, pts, what="params"):
+    """[B,M,12] CUDA parameters as contiguous float32, and M."""
+    _require_cuda(params)
+    if params.dim() != 3 or params.shape[0] != B or params.shape[2] != 12:
+        raise ValueError("%s must be [%d,M,12], got %s" % (what, B, tuple(params.shape)))
+    if params.device != pts.device:
+        raise ValueError("points and %s are on different devices" % what)
+    return params.detach().to(torch.float32).contiguous(), _parts(B, params.shape[1])
+
+
+def pts_seed(points, parts, count=None, lloyd=10):
+    """sqr_pts_seed -> (labels [B,P] i32, centres [B,M,3] f32, seeds [B,M] i32): farthest-point seeds and `lloyd`
+    Lloyd iterations.  One chain of launches on the current stream; no host wait."""
+    M = _parts_shapes(points, parts)
+    pts, cnt, B, P = _point_list(points, count)
+    dev = pts.device
+    if int(lloyd) < 0:
+        raise ValueError("lloyd must be >= 0, got %d" % lloyd)
+    label = torch.empty(B, P, dtype=torch.int32, device=dev)
+    centres = torch.empty(B, M, 3, dtype=torch.float32, device=dev)
+    seeds = torch.empty(B, M, dtype=torch.int32, device=dev)
+    L = lib()
+    wsb = L.sqr_pts_seed_workspace_bytes(B, P, M)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_seed(ptr(pts), ptr(cnt), B, P, M, int(lloyd), ptr(label), ptr(centres), ptr(seeds), ptr(ws), wsb,
+                         stream_ptr(dev)), "sqr_pts_seed")
+    return label, centres, seeds
+
+
+def pts_assign(points, params, count=None, labels_prev=None):
+    """sqr_pts_assign: params [B,M,12] -> dict: label [B,P] i32, dist [B,P] f32, part_count [B,M] i32, part_dist
+    [B,M] f64 and, with labels_prev [B,P] i32, changed [B] i32.  Two launches; no host wait."""
+    pts, cnt, B, P = _point_list(points, count)
+    p, M = _part_params(params, B, pts)
+    dev = pts.device
+    prev = _labels(labels_prev, pts, "labels_prev") if labels_prev is not None else None
+    out = {"label": torch.empty(B, P, dtype=torch.int32, device=dev),
+           "dist": torch.empty(B, P, dtype=torch.float32, device=dev),
+           "part_count": torch.empty(B, M, dtype=torch.int32, device=dev),
+           "part_dist": torch.empty(B, M, dtype=torch.float64, device=dev)}
+    if prev is not None:
+        out["changed"] = torch.empty(B, dtype=torch.int32, device=dev)
+    L = lib()
+    wsb = L.sqr_pts_assign_workspace_bytes(B, P, M)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_assign(ptr(pts), ptr(cnt), ptr(p), ptr(prev), B, P, M, ptr(out["label"]), ptr(out["dist"]),
+                           ptr(out["part_count"]), ptr(out["part_dist"]), ptr(out.get("changed")), ptr(ws), wsb,
+                           stream_ptr(dev)), "sqr_pts_assign")
+    return out
+
+
+def pts_labeled_lm_refine(points, count, labels, params, iters, lambda0, up, down):
+    """sqr_pts_labeled_lm_refine: params [K,B,M,12] (or [B,M,12] = one slice) -> (params [K,B,M,12] f32,
+    energy_before [K,B,M] f64, energy_after [K,B,M] f64, accepted [K,B,M] i32): pts_lm_refine on the parts of the
+    labelled lists."""
+    pts, cnt, B, P = _point_list(points, count)
+    lab = _labels(labels, pts)
+    _require_cuda(params)
+    p = params.detach().to(torch.float32)
+    if p.dim() == 3:
+        p = p[None]
+    if p.dim() != 4 or p.shape[0] < 1 or p.shape[1] != B or p.shape[3] != 12:
+        raise ValueError("params must be [K,%d,M,12] or [%d,M,12], got %s" % (B, B, tuple(params.shape)))
+    p = p.contiguous()
+    K, M, dev = int(p.shape[0]), _parts(B, p.shape[2]), pts.device
+    out = torch.empty(K, B, M, 12, dtype=torch.float32, device=dev)
+    before = torch.empty(K, B, M, dtype=torch.float64, device=dev)
+    after = torch.empty(K, B, M, dtype=torch.float64, device=dev)
+    accepted = torch.empty(K, B, M, dtype=torch.int32, device=dev)
+    L = lib()
+    wsb = L.sqr_pts_labeled_lm_refine_workspace_bytes(K * B * M, P)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_labeled_lm_refine(ptr(p), ptr(pts), ptr(cnt), ptr(lab), K, B, P, M, int(iters), float(lambda0),
+                                      float(up), float(down), ptr(out), ptr(before), ptr(after), ptr(accepted),
+                                      ptr(ws), wsb, stream_ptr(dev)), "sqr_pts_labeled_lm_refine")
+    return out, before, after, accepted
+
+
+def pts_labeled_recover(points, count, labels, parts, iters, e0, lambda0, up, down):
+    """sqr_pts_labeled_recover -> (params [B,M,12] f32, energy [B,M] f64, index [B,M] i32, info dict: starts, params
+    [3,B,M,12] f32, energy_before, energy_after [3,B,M] f64, accepted [3,B,M] i32): pts_recover on the parts of the
+    labelled lists."""
+    M = _parts_shapes(points, parts, labels)
+    pts, cnt, B, P = _point_list(points, count)
+    lab = _labels(labels, pts)
+    dev, K = pts.device, 3
+    f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=dev)  # noqa: E731
+    out = torch.empty(B, M, 12, dtype=torch.float32, device=dev)
+    energy = f64(B, M)
+    index = torch.empty(B, M, dtype=torch.int32, device=dev)
+    info = {"starts": torch.empty(K, B, M, 12, dtype=torch.float32, device=dev),
+            "params": torch.empty(K, B, M, 12, dtype=torch.float32, device=dev),
+            "energy_before": f64(K, B, M), "energy_after": f64(K, B, M),
+            "accepted": torch.empty(K, B, M, dtype=torch.int32, device=dev)}
+    L = lib()
+    wsb = L.sqr_pts_labeled_recover_workspace_bytes(K, B * M, P)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_labeled_recover(ptr(pts), ptr(cnt), ptr(lab), B, P, M, int(iters), float(e0), ptr(None), 0,
+                                    float(lambda0), float(up), float(down), ptr(out), ptr(energy), ptr(index),
+                                    ptr(info["starts"]), ptr(info["params"]), ptr(info["energy_before"]),
+                                    ptr(info["energy_after"]), ptr(info["accepted"]), ptr(ws), wsb, stream_ptr(dev)),
+          "sqr_pts_labeled_recover")
+    return out, energy, index, info
+
+
+def pts_recover_parts(points, count, parts, labels, rounds, iters0, iters, lloyd, e0, lambda0, up, down):
+    """sqr_pts_recover_parts -> (params [B,M,12] f32, labels [B,P] i32, energy [B,M] f64, info dict: dist [B,P]
+    f32, part_count [B,M] i32, part_dist [B,M] f64, changed [rounds,B] i32 and, when labels is None (it seeded),
+    seeds [B,M] i32 and centres [B,M,3] f32).  One chain of launches on the current stream; no host wait."""
+    M, T = _parts_shapes(points, parts, labels), int(rounds)
+    if not 1 <= T <= 1024:
+        raise ValueError("rounds must be in [1,1024], got %d" % T)
+    pts, cnt, B, P = _point_list(points, count)
+    lab_in = _labels(labels, pts) if labels is not None else None
+    dev = pts.device
+    out = torch.empty(B, M, 12, dtype=torch.float32, device=dev)
+    label = torch.empty(B, P, dtype=torch.int32, device=dev)
+    energy = torch.empty(B, M, dtype=torch.float64, device=dev)
+    info = {"dist": torch.empty(B, P, dtype=torch.float32, device=dev),
+            "part_count": torch.empty(B, M, dtype=torch.int32, device=dev),
+            "part_dist": torch.empty(B, M, dtype=torch.float64, device=dev),
+            "changed": torch.empty(T, B, dtype=torch.int32, device=dev)}
+    if lab_in is None:
+        info["seeds"] = torch.empty(B, M, dtype=torch.int32, device=dev)
+        info["centres"] = torch.empty(B, M, 3, dtype=torch.float32, device=dev)
+    L = lib()
+    wsb = L.sqr_pts_recover_parts_workspace_bytes(B, P, M)
+    ws = _workspace(wsb, dev)
+    check(L.sqr_pts_recover_parts(ptr(pts), ptr(cnt), ptr(lab_in), B, P, M, T, int(iters0), int(iters), int(lloyd),
+                                  float(e0), float(lambda0), float(up), float(down), ptr(out), ptr(label), ptr(energy),
+                                  ptr(info["dist"]), ptr(info["part_count"]), ptr(info["part_dist"]),
+                                  ptr(info["changed"]), ptr(info.get("seeds")), ptr(info.get("centres")), ptr(ws), wsb,
+                                  stream_ptr(dev)), "sqr_pts_recover_parts")
+    return out, label, energy, info
+
+
 def implicit_render(params, R, tau=1.0, sharpness=100.0):
     """depth_projection (classes.py:232-282) -> [B,R,R] float32 images (no autograd)."""
     _require_cuda(params)

@@ -46,7 +46,16 @@ everything twice and prints one JSON line per pass.
 times the point-list stack at B = 64, P = 4096 (the slots of the recover mode's R = 64 scanner-style images, as a
 list in pixel order), 30 iterations: sqr.fit.recover_points next to sqr.fit.recover on the same images, eagerly and
 inside a replayed graph, and losses.point_energy forward + backward next to LeastSquares.energy_function (plain
-torch, forward + backward) on the same CUDA point lists.  Everything twice in one process, one JSON line per pass."""
+torch, forward + backward) on the same CUDA point lists.  Everything twice in one process, one JSON line per pass.
+
+    python tools/loss_time.py parts
+
+times sqr.fit.recover_parts at B = 8 clouds of M = 4 bodies, P = 4096, 3 rounds, eagerly and inside a replayed
+graph, next to the same fits done with the single-body calls in the same process: recover_points, then
+refine_points, on the B M NaN-masked copies of the clouds, the assignment between the rounds in torch ops, from
+precomputed seeding labels (so the chain is also timed from those labels, without its seeding); and the assignment
+kernel alone, and one normal-equations evaluation of the B M parts next to one of the B clouds (the M-fold walk of
+the part source).  Everything twice in one process, one JSON line per pass."""
 import json
 import os
 import sys
@@ -305,9 +314,105 @@ def points(dev, R=64, H=256, B=64, iters=30):
     return res
 
 
+PART_CENTRES = ((0.25, 0.25, 0.3), (0.75, 0.3, 0.6), (0.45, 0.75, 0.5), (0.75, 0.75, 0.25))
+
+
+def _parts_scene(dev, B, M, per_body):
+    """B clouds of M bodies: golden clouds (b + m) mod 8 shrunk by 0.7 about their labels' t and moved to
+    PART_CENTRES, every cloud's 512 points repeated to per_body, the M per_body slots permuted."""
+    d = np.load(os.path.join(ROOT, "tests", "golden", "points.npz"), allow_pickle=False)
+    rng = np.random.default_rng(1)
+    pts = np.empty((B, M * per_body, 3), np.float32)
+    for b in range(B):
+        bodies = []
+        for m in range(M):
+            i = (b + m) % 8
+            cloud = (d["clouds"][i].astype(np.float64) - d["labels"][i][5:8]) * 0.7 + np.array(PART_CENTRES[m])
+            bodies.append(np.tile(cloud, (-(-per_body // 512), 1))[:per_body])
+        pts[b] = np.concatenate(bodies)[rng.permutation(M * per_body)]
+    return torch.tensor(pts, device=dev)
+
+
+def _torch_assign(pts, par):
+    """sqr_pts_assign's labels in plain torch ops (no host wait): pts [B,P,3], par [B,M,12] -> [B,P] i32."""
+    a, e = par[..., 0:3].clamp(0.05, 1), par[..., 3:5].clamp(0.1, 1)
+    t = par[..., 5:8].clamp(0, 1)
+    x, y, z, w = -par[..., 8], -par[..., 9], -par[..., 10], par[..., 11]
+    rot = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
+                       2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
+                       2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).reshape(*par.shape[:2], 3, 3)
+    d = pts[:, None] - t[:, :, None]
+    v = torch.einsum("bmij,bmpj->bmpi", rot, d) / a[:, :, None]
+    sq = v * v
+    sq = torch.where(sq == 0, sq + 1e-4, sq)
+    e1, e2 = e[..., 0, None], e[..., 1, None]
+    f = ((sq[..., 0] ** (1 / e2) + sq[..., 1] ** (1 / e2)) ** (e2 / e1) + sq[..., 2] ** (1 / e1)) ** e1
+    dist = d.norm(dim=-1) * (1 - f ** -0.5).abs()
+    on = torch.isfinite(pts).all(-1)
+    dist = torch.where(torch.isfinite(dist), dist, torch.full_like(dist, float("inf")))
+    return torch.where(on, dist.argmin(1), torch.full_like(on, -1, dtype=torch.int64)).to(torch.int32)
+
+
+def parts(dev, B=8, M=4, P=4096, rounds=3, iters0=30, iters=10):
+    """sqr.fit.recover_parts eagerly and inside a replayed graph, next to what could be done before it with the
+    same fits: recover_points then refine_points on the B M NaN-masked copies of the clouds, the assignment between
+    the rounds in torch ops, from the same (precomputed) seeding labels; the assignment kernel alone next to those
+    torch ops; and one part's normal-equations launch (B M virtual clouds) next to one cloud's (B clouds)."""
+    from sqr import fit
+    pts = _parts_scene(dev, B, M, P // M)
+    seed_labels, _, _ = losses.pts_seed(pts, M)
+    nan = torch.full_like(pts, float("nan"))
+    part_ids = torch.arange(M, device=dev, dtype=torch.int32)[None, :, None]
+
+    def masked(labels):
+        return torch.where((labels[:, None, :] == part_ids)[..., None], pts[:, None], nan[:, None]).reshape(B * M, P, 3)
+
+    def baseline():
+        labels = seed_labels
+        par = fit.recover_points(masked(labels), iters=iters0)[0]
+        labels = _torch_assign(pts, par.reshape(B, M, 12))
+        for _ in range(1, rounds):
+            par = fit.refine_points(masked(labels), par, iters=iters)[0]
+            labels = _torch_assign(pts, par.reshape(B, M, 12))
+        return par.reshape(B, M, 12), labels
+
+    chain = lambda: fit.recover_parts(pts, M, rounds=rounds, iters0=iters0, iters=iters)  # noqa: E731
+    chain_given = lambda: fit.recover_parts(pts, M, rounds=rounds, iters0=iters0, iters=iters,  # noqa: E731
+                                            labels=seed_labels)
+    par, labels, energy, info = fit.recover_parts(pts, M, rounds=rounds, iters0=iters0, iters=iters, return_info=True)
+    bpar, blabels = baseline()
+    flat = par.reshape(B * M, 12).contiguous()
+    res = {"shape": "B%d_M%d_P%d" % (B, M, P), "rounds": rounds, "iters0": iters0, "iters": iters,
+           "changed_per_round": info["changed"].sum(1).tolist(),
+           "baseline_labels_equal": bool(torch.equal(labels, blabels)),
+           "baseline_params_equal_bitwise": bool(torch.equal(par, bpar)),
+           "energy_max": energy.max().item(),
+           "recover_parts_eager_ms": round(_eager_ms(chain), 4),
+           "recover_parts_from_labels_eager_ms": round(_eager_ms(chain_given), 4),
+           "baseline_eager_ms": round(_eager_ms(baseline), 4),
+           "recover_parts_in_graph_us": round(_graph_us(chain), 2),
+           "recover_parts_from_labels_in_graph_us": round(_graph_us(chain_given), 2),
+           "baseline_in_graph_us": round(_graph_us(baseline), 2),
+           "seed_in_graph_us": round(_graph_us(lambda: losses.pts_seed(pts, M)), 2),
+           "assign_in_graph_us": round(_graph_us(lambda: losses.pts_assign(pts, par), reps=200), 2),
+           "torch_assign_in_graph_us": round(_graph_us(lambda: _torch_assign(pts, par), reps=200), 2),
+           "normal_eq_parts_in_graph_us": round(_graph_us(
+               lambda: losses.pts_labeled_lm_refine(pts, None, labels, par, 0, 1e-3, 10.0, 0.1), reps=200), 2),
+           "normal_eq_clouds_in_graph_us": round(_graph_us(
+               lambda: losses.pts_lm_refine(pts, None, flat[:B].contiguous(), 0, 1e-3, 10.0, 0.1), reps=200), 2)}
+    res["recover_parts_over_baseline_in_graph"] = round(
+        res["recover_parts_from_labels_in_graph_us"] / res["baseline_in_graph_us"], 4)
+    return res
+
+
 def main():
     dev = torch.device("cuda", 0)
     out = {"env": {k: v for k, v in os.environ.items() if k.startswith("SQR_")}}
+    if sys.argv[1:] == ["parts"]:
+        for _ in range(2):  # every figure twice in one process: one JSON line per pass
+            out["parts"] = parts(dev)
+            print(json.dumps(out))
+        return
     if sys.argv[1:] == ["online"]:
         for _ in range(2):  # every figure twice in one process: one JSON line per pass
             out["online"] = online(dev)
