@@ -1443,40 +1443,6 @@ __global__ void __launch_bounds__(256) add_inplace_kernel(T* __restrict__ dx, co
   }
 }
 
-static int bwd_data_impl(const void* dy, const void* w_crsk, void* dx, const void* addend, const sqr_conv_desc* d,
-                         void* stream) {
-  Shape sh;
-  int rc = check_desc(d, &sh);
-  if (rc) return rc;
-  SQR_CHECK_ARG(!sh.im2col, "conv2d_bwd_data: C=%d < 8 not supported", d->C);
-  SQR_CHECK_ARG(dy && w_crsk && dx, "conv2d_bwd_data: null pointer");
-  SQR_CHECK_ARG(addend != dx, "conv2d_bwd_data_acc: addend must not alias dx");
-  hipStream_t st = as_stream(stream);
-  if (direct3(d, sh)) {
-    Conv3Call c = conv3_call(d, st, dy, w_crsk, dx, true);
-    c.addend = addend;
-    rc = conv3_launch(c);
-    if (rc != kNotHandled) return rc;
-  }
-  rc = direct3s2_dgrad(d, sh, st, dy, w_crsk, dx, addend, 0);
-  if (rc != kNotHandled) return rc;
-  rc = bwd_data_gemm(dy, w_crsk, dx, d, sh, st);
-  if (rc || !addend) return rc;
-  const long long n = (long long)d->N * d->H * d->W * d->C;
-  const unsigned grid = (unsigned)((n + 1023) / 1024);
-  SQR_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL(add_inplace_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)dx,
-                                                     (const T*)addend, n));
-  SQR_HIP_LAUNCH_CHECK("add_inplace_kernel");
-  return 0;
-}
-
-extern "C" int sqr_conv2d_bwd_data(const void* dy, const void* w_crsk, void* dx, const sqr_conv_desc* d,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-  (void)workspace;
-  (void)workspace_bytes;
-  return bwd_data_impl(dy, w_crsk, dx, nullptr, d, stream);
-}
-
 // dx[n, 2i, 2j, c] += addend_c[n, i, j, c]: the fallback of sqr_conv2d_bwd_data_acc_s2
 template <typename T>
 __global__ void __launch_bounds__(256) add_s2_compact_kernel(T* __restrict__ dx, const T* __restrict__ ac, int Ho,
@@ -1491,60 +1457,98 @@ __global__ void __launch_bounds__(256) add_s2_compact_kernel(T* __restrict__ dx,
   dx[o] = (T)((float)dx[o] + (float)ac[i]);
 }
 
+// The route of all six backward-data entries, their own argument checks done.  c describes the call and
+// what the entry wants beyond dx = dgrad(dy) (c.addend / addend_mask / bnb + stats), addend_c is a compact
+// [N][H/2][W/2][C] addend for the (even, even) pixels.  The direct kernels fuse these into their
+// epilogues: 3x3 / stride 1 (anything but addend_c), then 3x3 / stride 2 (nothing, or either addend).
+// Where neither takes the call: SQR_E_UNSUPPORTED with the entry's text, or for the entries without one
+// the plain route and the epilogue as a kernel of its own.
+static int dgrad_route(const sqr_conv_desc* d, const Shape& sh, const Conv3Call& c, const void* addend_c,
+                       const char* unsupported) {
+  int rc = kNotHandled;
+  if (!addend_c && direct3(d, sh)) rc = conv3_launch(c);
+  if (rc == kNotHandled && !c.addend_mask && !c.bnb)
+    rc = direct3s2_dgrad(d, sh, c.st, c.x, c.w, c.out, addend_c ? addend_c : c.addend, addend_c ? 1 : 0);
+  if (rc != kNotHandled) return rc;
+  if (unsupported) {
+    set_error("%s", unsupported);
+    return SQR_E_UNSUPPORTED;
+  }
+  // the plain route ends in the implicit GEMM (the attempts above were its direct kernels already, unless
+  // they were asked for a compact addend or the BatchNorm sums)
+  if (addend_c || c.bnb)
+    rc = dgrad_route(d, sh, conv3_call(d, c.st, c.x, c.w, c.out, true), nullptr, nullptr);
+  else
+    rc = bwd_data_gemm(c.x, c.w, c.out, d, sh, c.st);
+  if (rc) return rc;
+  if (c.bnb)
+    return bn_mask_reduce(c.out, c.bnb->x, c.bnb->mask, c.bnb->mean, (long long)d->N * d->H * d->W, d->C, d->dtype,
+                          c.stats, c.stats_rows, c.st);
+  if (c.addend) {
+    const long long n = (long long)d->N * d->H * d->W * d->C;
+    const unsigned grid = (unsigned)((n + 1023) / 1024);
+    SQR_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL(add_inplace_kernel<T>, dim3(grid), dim3(256), 0, c.st,
+                                                       (T*)c.out, (const T*)c.addend, n));
+    SQR_HIP_LAUNCH_CHECK("add_inplace_kernel");
+  }
+  if (addend_c) {
+    const long long n = (long long)d->N * sh.Ho * sh.Wo * d->C;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    SQR_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL(add_s2_compact_kernel<T>, dim3(grid), dim3(256), 0, c.st,
+                                                       (T*)c.out, (const T*)addend_c, sh.Ho, sh.Wo, d->C, n));
+    SQR_HIP_LAUNCH_CHECK("add_s2_compact_kernel");
+  }
+  return 0;
+}
+
+static int bwd_data_impl(const void* dy, const void* w_crsk, void* dx, const void* addend, const sqr_conv_desc* d,
+                         void* stream) {
+  Shape sh;
+  int rc = check_desc(d, &sh);
+  if (rc) return rc;
+  SQR_CHECK_ARG(!sh.im2col, "conv2d_bwd_data: C=%d < 8 not supported", d->C);
+  SQR_CHECK_ARG(dy && w_crsk && dx, "conv2d_bwd_data: null pointer");
+  SQR_CHECK_ARG(addend != dx, "conv2d_bwd_data_acc: addend must not alias dx");
+  Conv3Call c = conv3_call(d, as_stream(stream), dy, w_crsk, dx, true);
+  c.addend = addend;
+  return dgrad_route(d, sh, c, nullptr, nullptr);
+}
+
+extern "C" int sqr_conv2d_bwd_data(const void* dy, const void* w_crsk, void* dx, const sqr_conv_desc* d, void*,
+                                   size_t, void* stream) {
+  return bwd_data_impl(dy, w_crsk, dx, nullptr, d, stream);
+}
+
+extern "C" int sqr_conv2d_bwd_data_acc(const void* dy, const void* w_crsk, void* dx, const void* addend,
+                                       const sqr_conv_desc* d, void*, size_t, void* stream) {
+  SQR_CHECK_ARG(addend, "conv2d_bwd_data_acc: null addend");
+  return bwd_data_impl(dy, w_crsk, dx, addend, d, stream);
+}
+
 extern "C" int sqr_conv2d_bwd_data_acc_s2(const void* dy, const void* w_crsk, void* dx, const void* addend_c,
-                                          const sqr_conv_desc* d, void* workspace, size_t workspace_bytes,
-                                          void* stream) {
-  (void)workspace;
-  (void)workspace_bytes;
+                                          const sqr_conv_desc* d, void*, size_t, void* stream) {
   Shape sh;
   int rc = check_desc(d, &sh);
   if (rc) return rc;
   SQR_CHECK_ARG(dy && w_crsk && dx && addend_c, "conv2d_bwd_data_acc_s2: null pointer");
   SQR_CHECK_ARG(d->stride == 2 && d->H == 2 * sh.Ho && d->W == 2 * sh.Wo && !sh.im2col,
                 "conv2d_bwd_data_acc_s2: needs a stride-2 conv with H = 2 Ho, W = 2 Wo");
-  hipStream_t st = as_stream(stream);
-  rc = direct3s2_dgrad(d, sh, st, dy, w_crsk, dx, addend_c, 1);
-  if (rc != kNotHandled) return rc;
-  rc = bwd_data_impl(dy, w_crsk, dx, nullptr, d, stream);
-  if (rc) return rc;
-  const long long n = (long long)d->N * sh.Ho * sh.Wo * d->C;
-  const unsigned grid = (unsigned)((n + 255) / 256);
-  SQR_DISPATCH_DTYPE(d->dtype, T, hipLaunchKernelGGL(add_s2_compact_kernel<T>, dim3(grid), dim3(256), 0, st, (T*)dx,
-                                                     (const T*)addend_c, sh.Ho, sh.Wo, d->C, n));
-  SQR_HIP_LAUNCH_CHECK("add_s2_compact_kernel");
-  return 0;
-}
-
-extern "C" int sqr_conv2d_bwd_data_acc(const void* dy, const void* w_crsk, void* dx, const void* addend,
-                                       const sqr_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-  (void)workspace;
-  (void)workspace_bytes;
-  SQR_CHECK_ARG(addend, "conv2d_bwd_data_acc: null addend");
-  return bwd_data_impl(dy, w_crsk, dx, addend, d, stream);
+  return dgrad_route(d, sh, conv3_call(d, as_stream(stream), dy, w_crsk, dx, true), addend_c, nullptr);
 }
 
 extern "C" int sqr_conv2d_bwd_data_acc_masked(const void* dy, const void* w_crsk, void* dx, const void* addend,
-                                              const uint8_t* addend_mask, const sqr_conv_desc* d, void* workspace,
-                                              size_t workspace_bytes, void* stream) {
-  (void)workspace;
-  (void)workspace_bytes;
+                                              const uint8_t* addend_mask, const sqr_conv_desc* d, void*, size_t,
+                                              void* stream) {
   Shape sh;
   int rc = check_desc(d, &sh);
   if (rc) return rc;
   SQR_CHECK_ARG(dy && w_crsk && dx && addend && addend_mask, "conv2d_bwd_data_acc_masked: null pointer");
   SQR_CHECK_ARG(addend != dx, "conv2d_bwd_data_acc_masked: addend must not alias dx");
-  rc = kNotHandled;
-  if (direct3(d, sh)) {
-    Conv3Call c = conv3_call(d, as_stream(stream), dy, w_crsk, dx, true);
-    c.addend = addend;
-    c.addend_mask = addend_mask;
-    rc = conv3_launch(c);
-  }
-  if (rc == kNotHandled) {
-    set_error("conv2d_bwd_data_acc_masked: only the direct 3x3 / stride-1 16-bit kernels take a masked addend");
-    return SQR_E_UNSUPPORTED;
-  }
-  return rc;
+  Conv3Call c = conv3_call(d, as_stream(stream), dy, w_crsk, dx, true);
+  c.addend = addend;
+  c.addend_mask = addend_mask;
+  return dgrad_route(d, sh, c, nullptr,
+                     "conv2d_bwd_data_acc_masked: only the direct 3x3 / stride-1 16-bit kernels take a masked addend");
 }
 
 extern "C" size_t sqr_conv2d_bwd_data_bn_stats_floats(const sqr_conv_desc* d) {
@@ -1560,29 +1564,19 @@ extern "C" size_t sqr_conv2d_bwd_data_bn_stats_floats(const sqr_conv_desc* d) {
 
 extern "C" int sqr_conv2d_bwd_data_bn(const void* dy, const void* w_crsk, void* g_out, const void* bn_x,
                                       const uint8_t* relu_mask, const float* bn_mean, float* stats, int* stats_rows,
-                                      const sqr_conv_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-  (void)workspace;
-  (void)workspace_bytes;
+                                      const sqr_conv_desc* d, void*, size_t, void* stream) {
   Shape sh;
   int rc = check_desc(d, &sh);
   if (rc) return rc;
   SQR_CHECK_ARG(!sh.im2col, "conv2d_bwd_data_bn: C=%d < 8 not supported", d->C);
   SQR_CHECK_ARG(dy && w_crsk && g_out && bn_x && relu_mask && bn_mean && stats && stats_rows,
                 "conv2d_bwd_data_bn: null pointer");
-  hipStream_t st = as_stream(stream);
-  if (direct3(d, sh)) {
-    const BnbArgs bnb = {bn_x, relu_mask, bn_mean};
-    Conv3Call c = conv3_call(d, st, dy, w_crsk, g_out, true);
-    c.stats = stats;
-    c.stats_rows = stats_rows;
-    c.bnb = &bnb;
-    rc = conv3_launch(c);
-    if (rc != kNotHandled) return rc;
-  }
-  rc = bwd_data_impl(dy, w_crsk, g_out, nullptr, d, stream);
-  if (rc) return rc;
-  return bn_mask_reduce(g_out, bn_x, relu_mask, bn_mean, (long long)d->N * d->H * d->W, d->C, d->dtype, stats,
-                        stats_rows, st);
+  const BnbArgs bnb = {bn_x, relu_mask, bn_mean};
+  Conv3Call c = conv3_call(d, as_stream(stream), dy, w_crsk, g_out, true);
+  c.bnb = &bnb;
+  c.stats = stats;
+  c.stats_rows = stats_rows;
+  return dgrad_route(d, sh, c, nullptr, nullptr);
 }
 
 extern "C" int sqr_conv2d_bnin_nso_supported(const sqr_conv_desc* d) {
@@ -1607,15 +1601,11 @@ extern "C" int sqr_conv2d_bwd_data_bn_act(const void* dy, const void* w_crsk, vo
   bnb.coef = bn_coef;
   bnb.act = act_out;
   Conv3Call c = conv3_call(d, as_stream(stream), dy, w_crsk, g_out, true);
+  c.bnb = &bnb;
   c.stats = stats;
   c.stats_rows = stats_rows;
-  c.bnb = &bnb;
-  rc = conv3_launch(c);
-  if (rc == kNotHandled) {
-    set_error("conv2d_bwd_data_bn_act: no direct kernel for this shape (sqr_conv2d_bnin_nso_supported)");
-    return SQR_E_UNSUPPORTED;
-  }
-  return rc;
+  return dgrad_route(d, sh, c, nullptr,
+                     "conv2d_bwd_data_bn_act: no direct kernel for this shape (sqr_conv2d_bnin_nso_supported)");
 }
 
 // implicit-GEMM backward-data over the output parity classes

@@ -8,7 +8,9 @@ torch/models.py:134-184).  Each forward packs the weight into the kernel layouts
 Compute dtype: bfloat16 / float16 when the input has that dtype or CUDA autocast is on with it,
 else float32 (exact-f32 MFMA: the parity mode).
 """
+import ctypes
 import os
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -84,20 +86,17 @@ def _desc(N, C, H, W, K, R, S, stride, pad, dtype):
 
 
 def _out_hw(d):
-    import ctypes
     ho, wo = ctypes.c_int(), ctypes.c_int()
     check(lib().sqr_conv2d_out_hw(ctypes.byref(d), ctypes.byref(ho), ctypes.byref(wo)), "sqr_conv2d_out_hw")
     return ho.value, wo.value
 
 
 def _ws(d, which, device):
-    import ctypes
     n = lib().sqr_conv2d_workspace_bytes(ctypes.byref(d), which)
     return torch.empty(max(n, 16), dtype=torch.uint8, device=device), n
 
 
 def pack_weight(weight, d, need_crsk):
-    import ctypes
     K, C, R, S = weight.shape
     dt = _TORCH_DT[d.dtype]
     w = weight.detach().to(torch.float32).contiguous()
@@ -176,12 +175,16 @@ def pack_all(convs, dtype):
         mark_packed(m, dtype)
 
 
+def _partials(st, rows, C):
+    """The [rows, 2, C] partial rows at the start of a statistics buffer (rows: the c_int the entry set)."""
+    return st[:rows.value * 2 * C].view(rows.value, 2, C)
+
+
 def conv2d_fwd(x, w_krsc, d, return_ws=False, stats=False):
     """y = conv(x); with return_ws the workspace (holding the im2col matrix for C<8) is returned
     too; with stats the BatchNorm partials [rows, 2, K] (f32 per-tile Welford rows (mean, M2) of y,
     their pixel counts after them in the buffer: sqr.bn.partial_counts; sqr_conv2d_fwd_stats) are
     returned after y."""
-    import ctypes
     ho, wo = _out_hw(d)
     dt = _TORCH_DT[d.dtype]
     y = torch.empty((d.N, d.K, ho, wo), dtype=dt, device=x.device, memory_format=_CL)
@@ -200,7 +203,7 @@ def conv2d_fwd(x, w_krsc, d, return_ws=False, stats=False):
                                       stream_ptr(x.device))
     check(rc, "sqr_conv2d_fwd")
     if stats:
-        st = st[:rows.value * 2 * d.K].view(rows.value, 2, d.K)
+        st = _partials(st, rows, d.K)
         return (y, st, ws) if return_ws else (y, st)
     return (y, ws) if return_ws else y
 
@@ -210,7 +213,6 @@ def conv2d_fwd_bnin(x_pre, coef, x_act, mask, w_krsc, d):
     the conv stages its input; x_act and mask receive that activation and its ReLU mask, or are both
     None: no side outputs (sqr_conv2d_fwd_stats_bnin).  None where the kernel does not take the shape
     (nothing written)."""
-    import ctypes
     ho, wo = _out_hw(d)
     dt = _TORCH_DT[d.dtype]
     y = torch.empty((d.N, d.K, ho, wo), dtype=dt, device=x_pre.device, memory_format=_CL)
@@ -223,26 +225,41 @@ def conv2d_fwd_bnin(x_pre, coef, x_act, mask, w_krsc, d):
     if rc == -2:  # SQR_E_UNSUPPORTED
         return None
     check(rc, "sqr_conv2d_fwd_stats_bnin")
-    return y, st[:rows.value * 2 * d.K].view(rows.value, 2, d.K)
+    return y, _partials(st, rows, d.K)
+
+
+def _bwd_data(entry, gy, w_crsk, d, *operands, stats=False, ws=True, may_refuse=False):
+    """The one call of the backward-data entries, which all read
+    (dy, w_crsk, dx, operands..., [stats, &rows,] &desc, [workspace, bytes,] stream): dx, or with stats
+    (dx, the BatchNorm backward partials [rows, 2, C]); None where an entry that may_refuse answers
+    SQR_E_UNSUPPORTED (nothing written)."""
+    L = lib()
+    dx = torch.empty((d.N, d.C, d.H, d.W), dtype=_TORCH_DT[d.dtype], device=gy.device, memory_format=_CL)
+    args = [ptr(gy), ptr(w_crsk), ptr(dx)] + [ptr(t) for t in operands]
+    if stats:
+        st = torch.empty(L.sqr_conv2d_bwd_data_bn_stats_floats(ctypes.byref(d)), dtype=torch.float32, device=gy.device)
+        rows = ctypes.c_int()
+        args += [ptr(st), ctypes.byref(rows)]
+    args.append(ctypes.byref(d))
+    if ws:
+        buf, n = _ws(d, 1, gy.device)
+        args += [ptr(buf), n]
+    with _Probe("dgrad", d):
+        rc = getattr(L, entry)(*args, stream_ptr(gy.device))  # by name, at call time: tests wrap the entries
+    if may_refuse and rc == -2:  # SQR_E_UNSUPPORTED
+        return None
+    check(rc, entry)
+    return (dx, _partials(st, rows, d.C)) if stats else dx
 
 
 def conv2d_bwd_data(gy, w_crsk, d):
-    import ctypes
-    dt = _TORCH_DT[d.dtype]
-    dx = torch.empty((d.N, d.C, d.H, d.W), dtype=dt, device=gy.device, memory_format=_CL)
-    ws, n = _ws(d, 1, gy.device)
-    with _Probe("dgrad", d):
-        rc = lib().sqr_conv2d_bwd_data(ptr(gy), ptr(w_crsk), ptr(dx), ctypes.byref(d), ptr(ws), n,
-                                       stream_ptr(gy.device))
-    check(rc, "sqr_conv2d_bwd_data")
-    return dx
+    return _bwd_data("sqr_conv2d_bwd_data", gy, w_crsk, d)
 
 
 def conv2d_bwd_weight(x, gy, d, col=None, wid=None, fin=None, red=None):
     """dW (fp32, [K,C,R,S]); for C<8 convs pass the forward's workspace as `col` to skip im2col;
     `wid` = id of the weight parameter (its sqr.gradbuf slot, if any, receives dW); `fin` / `red`:
     sqr_bn_bwd_fin / sqr_bn_bwd_red jobs riding the same launch (sqr_conv2d_bwd_weight_bn)."""
-    import ctypes
     dw = gradbuf.out(wid, (d.K, d.C, d.R, d.S), gy.device)
     L = lib()
     n = L.sqr_conv2d_workspace_bytes(ctypes.byref(d), 2)
@@ -268,29 +285,19 @@ def conv2d_bwd_weight(x, gy, d, col=None, wid=None, fin=None, red=None):
 def conv2d_bwd_data_acc(gy, w_crsk, d, addend):
     """bwd_data(gy) + addend in one pass (sqr_conv2d_bwd_data_acc: the direct kernels add in their
     epilogues)."""
-    import ctypes
-    dt = _TORCH_DT[d.dtype]
-    dx = torch.empty((d.N, d.C, d.H, d.W), dtype=dt, device=gy.device, memory_format=_CL)
-    ws, n = _ws(d, 1, gy.device)
-    with _Probe("dgrad", d):
-        rc = lib().sqr_conv2d_bwd_data_acc(ptr(gy), ptr(w_crsk), ptr(dx), ptr(addend), ctypes.byref(d), ptr(ws), n,
-                                           stream_ptr(gy.device))
-    check(rc, "sqr_conv2d_bwd_data_acc")
-    return dx
+    return _bwd_data("sqr_conv2d_bwd_data_acc", gy, w_crsk, d, addend)
 
 
 def conv2d_bwd_data_acc_s2(gy, w_crsk, d, addend_c):
     """bwd_data(gy) of a stride-2 conv + a compact [N, C, H/2, W/2] addend on the (even, even)
     pixels (sqr_conv2d_bwd_data_acc_s2: a stride-2 1x1 downsample branch's input gradient)."""
-    import ctypes
-    dt = _TORCH_DT[d.dtype]
-    dx = torch.empty((d.N, d.C, d.H, d.W), dtype=dt, device=gy.device, memory_format=_CL)
-    ws, n = _ws(d, 1, gy.device)
-    with _Probe("dgrad", d):
-        rc = lib().sqr_conv2d_bwd_data_acc_s2(ptr(gy), ptr(w_crsk), ptr(dx), ptr(addend_c), ctypes.byref(d), ptr(ws),
-                                              n, stream_ptr(gy.device))
-    check(rc, "sqr_conv2d_bwd_data_acc_s2")
-    return dx
+    return _bwd_data("sqr_conv2d_bwd_data_acc_s2", gy, w_crsk, d, addend_c)
+
+
+def conv2d_bwd_data_acc_masked(gy, w_crsk, d, masked):
+    """bwd_data(gy) + a MaskedGrad, masked while it is added (sqr_conv2d_bwd_data_acc_masked).  None where
+    the kernel does not take the shape (nothing written)."""
+    return _bwd_data("sqr_conv2d_bwd_data_acc_masked", gy, w_crsk, d, masked.dy, masked.mask, may_refuse=True)
 
 
 class CompactS2:
@@ -303,8 +310,11 @@ class CompactS2:
     def __init__(self, t, shape):
         self.t, self.shape = t, tuple(shape)
 
+    def to(self, dtype):
+        return CompactS2(self.t.to(dtype), self.shape)
+
     def full(self):
-        out = torch.zeros(self.shape, dtype=self.t.dtype, device=self.t.device, memory_format=_CL)
+        out = torch.empty(self.shape, dtype=self.t.dtype, device=self.t.device, memory_format=_CL).zero_()
         out[:, :, ::2, ::2] = self.t
         return out
 
@@ -312,18 +322,7 @@ class CompactS2:
 def conv2d_bwd_data_bn(gy, w_crsk, d, bn_x, bn_mask, bn_mean):
     """(g, partials): g = bwd_data(gy) * bn_mask and the following BatchNorm's backward sums
     [rows, 2, C] (sqr_conv2d_bwd_data_bn: the direct kernels compute both in their epilogues)."""
-    import ctypes
-    dt = _TORCH_DT[d.dtype]
-    g = torch.empty((d.N, d.C, d.H, d.W), dtype=dt, device=gy.device, memory_format=_CL)
-    L = lib()
-    st = torch.empty(L.sqr_conv2d_bwd_data_bn_stats_floats(ctypes.byref(d)), dtype=torch.float32, device=gy.device)
-    rows = ctypes.c_int()
-    ws, n = _ws(d, 1, gy.device)
-    with _Probe("dgrad", d):
-        rc = L.sqr_conv2d_bwd_data_bn(ptr(gy), ptr(w_crsk), ptr(g), ptr(bn_x), ptr(bn_mask), ptr(bn_mean), ptr(st),
-                                      ctypes.byref(rows), ctypes.byref(d), ptr(ws), n, stream_ptr(gy.device))
-    check(rc, "sqr_conv2d_bwd_data_bn")
-    return g, st[:rows.value * 2 * d.C].view(rows.value, 2, d.C)
+    return _bwd_data("sqr_conv2d_bwd_data_bn", gy, w_crsk, d, bn_x, bn_mask, bn_mean, stats=True)
 
 
 # A/B switch: 0 keeps the deferred BatchNorm output's side outputs (layer 1) / apply pass (layers 2-4)
@@ -333,7 +332,6 @@ _BN_NSO = os.environ.get("SQR_BN_NSO", "1") != "0"
 def bnin_nso_supported(d):
     """The conv of desc d can consume a deferred BatchNorm + ReLU output without it ever being written
     in the forward (sqr_conv2d_bnin_nso_supported)."""
-    import ctypes
     return _BN_NSO and bool(lib().sqr_conv2d_bnin_nso_supported(ctypes.byref(d)))
 
 
@@ -341,18 +339,8 @@ def conv2d_bwd_data_bn_act(gy, w_crsk, d, bn_x, bn_coef, bn_mean, act_out):
     """conv2d_bwd_data_bn for an input applied on load without side outputs: the ReLU mask is
     recomputed from bn_x and the forward coefficients, and act_out receives the activation
     (sqr_conv2d_bwd_data_bn_act)."""
-    import ctypes
-    dt = _TORCH_DT[d.dtype]
-    g = torch.empty((d.N, d.C, d.H, d.W), dtype=dt, device=gy.device, memory_format=_CL)
-    L = lib()
-    st = torch.empty(L.sqr_conv2d_bwd_data_bn_stats_floats(ctypes.byref(d)), dtype=torch.float32, device=gy.device)
-    rows = ctypes.c_int()
-    with _Probe("dgrad", d):
-        rc = L.sqr_conv2d_bwd_data_bn_act(ptr(gy), ptr(w_crsk), ptr(g), ptr(bn_x), ptr(bn_coef), ptr(bn_mean),
-                                          ptr(act_out), ptr(st), ctypes.byref(rows), ctypes.byref(d),
-                                          stream_ptr(gy.device))
-    check(rc, "sqr_conv2d_bwd_data_bn_act")
-    return g, st[:rows.value * 2 * d.C].view(rows.value, 2, d.C)
+    return _bwd_data("sqr_conv2d_bwd_data_bn_act", gy, w_crsk, d, bn_x, bn_coef, bn_mean, act_out, stats=True,
+                     ws=False)
 
 
 class BnBackwardLink:
@@ -425,7 +413,6 @@ class BnOutLink:
         return self.x_a is not None and self.mask is not None and (self.kind == 1 or self.x_b is not None)
 
     def red_job(self, dx):
-        import ctypes
         from ._lib import SqrBnBwdRed
         N, C, H, W = self.x_a.shape
         M = N * H * W
@@ -522,25 +509,86 @@ class ResidualJoin:
     def take(self):
         """conv1 side: the deposited gradient (or None: conv1 runs first, the branch returns its own)."""
         g, self.pending = self.pending, None
-        if g is None:
-            self.acc_done = True
-        else:
-            self.acc_done = False
+        self.acc_done = g is None
         return g
 
 
-class _MaskedDone:
-    """conv1's backward-data already added a MaskedGrad (the result dx)."""
+def _fits(a, d, dt):
+    """The addend a has the conv's dtype, full shape and channels-last layout, as the fused entries read
+    it: a tensor; a MaskedGrad on a 3x3 / stride 1 / pad 1 conv; a CompactS2 [N, C, H/2, W/2] on a
+    stride-2 conv with even H and W."""
+    t, inner, ok = a, (d.N, d.C, d.H, d.W), True
+    if isinstance(a, MaskedGrad):
+        t, ok = a.dy, (d.R, d.S, d.stride, d.pad) == (3, 3, 1, 1)
+    elif isinstance(a, CompactS2):
+        t, inner, ok = a.t, (d.N, d.C, d.H // 2, d.W // 2), d.stride == 2 and d.H % 2 == 0 and d.W % 2 == 0
+    return (ok and tuple(a.shape) == (d.N, d.C, d.H, d.W) and tuple(t.shape) == inner and t.dtype == dt
+            and t.is_contiguous(memory_format=_CL))
 
-    __slots__ = ("dx",)
 
-    def __init__(self, dx):
-        self.dx = dx
+# name: plain | acc | acc_masked | acc_s2 | bn | bn_act | compact (the table in DESIGN.md).  Before it runs,
+# expand: addend = addend.full() (and the route is chosen again for that tensor), materialize:
+# Deferred.materialize(); after it, add: dx + addend in Python; whole: dx is then the whole gradient of x
+DgradRoute = namedtuple("DgradRoute", "name expand materialize add whole", defaults=(False,) * 4)
 
 
-def ctypes_ref(d):
-    import ctypes
-    return ctypes.byref(d)
+def dgrad_route(d, dt, addend, link, deferred, xin, join, role):
+    """How a conv of desc d and compute dtype dt computes its input gradient.  addend: what join.take()
+    gave (role "acc"), link: the conv's BnBackwardLink, deferred: the sqr.bn.Deferred its forward applied
+    on load without side outputs, xin: its saved input (None: no weight gradient).  Launches nothing."""
+    if addend is not None:  # (a present addend disables the link routes)
+        if not _fits(addend, d, dt):
+            if isinstance(addend, torch.Tensor):
+                return DgradRoute("plain", add=True)
+            return DgradRoute("acc", expand=True, whole=True)
+        kind = {MaskedGrad: "acc_masked", CompactS2: "acc_s2"}.get(type(addend), "acc")
+        return DgradRoute(kind, whole=True)
+    if link is not None and link.ready() and link.x.dtype == dt:
+        if deferred is not None and link.deferred is deferred and not deferred.y_written \
+                and (xin is None or xin.data_ptr() == deferred.y.data_ptr()):
+            # applied on load without side outputs: the mask is recomputed, the activation written into xin
+            return DgradRoute("bn_act")
+        return DgradRoute("bn", materialize=deferred is not None)
+    if join is not None and role == "dep" and not join.acc_done and (d.R, d.S, d.stride, d.pad) == (1, 1, 2, 0) \
+            and d.H % 2 == 0 and d.W % 2 == 0 and d.C >= 8:
+        # stride-2 1x1 downsample: a stride-1 1x1 backward-data on the output grid, deposited as a CompactS2
+        return DgradRoute("compact")
+    return DgradRoute("plain")
+
+
+def _dgrad_run(ctx, route, g, xin, crsk, addend):
+    """Run the dgrad_route of Conv2dFn.backward: (dx or, route compact, a CompactS2; the route's whole)."""
+    d, link, deferred = ctx.d, ctx.bnb, ctx.deferred
+    dt = _TORCH_DT[d.dtype]
+    if route.name == "acc_masked":
+        dx = conv2d_bwd_data_acc_masked(g, crsk, d, addend)
+        if dx is not None:
+            return dx, route.whole
+        route = route._replace(expand=True)  # refused by the C entry: mask, then as any tensor addend
+    if route.expand:
+        addend = addend.full()
+        route = dgrad_route(d, dt, addend, link, deferred, xin, ctx.join, ctx.role)  # acc, or plain and add
+    if route.materialize:
+        deferred.materialize()
+    if route.name == "bn_act":
+        dx, link.stats = conv2d_bwd_data_bn_act(g, crsk, d, link.x, deferred.coef, link.mean, xin)
+        deferred.y_written = xin is not None  # the entry wrote the activation where it was given room
+        link.g = dx
+    elif route.name == "bn":
+        dx, link.stats = conv2d_bwd_data_bn(g, crsk, d, link.x, link.mask, link.mean)
+        link.g = dx
+    elif route.name == "acc_s2":
+        dx = conv2d_bwd_data_acc_s2(g, crsk, d, addend.t)
+    elif route.name == "acc":
+        dx = conv2d_bwd_data_acc(g, crsk, d, addend)
+    elif route.name == "compact":
+        d1 = _desc(d.N, d.C, d.H // 2, d.W // 2, d.K, 1, 1, 1, 0, dt)
+        dx = CompactS2(conv2d_bwd_data(g, crsk, d1), (d.N, d.C, d.H, d.W))
+    else:
+        dx = conv2d_bwd_data(g, crsk, d)
+        if route.add:
+            dx = dx + addend
+    return dx, route.whole
 
 
 def compute_dtype(x):
@@ -625,71 +673,18 @@ class Conv2dFn(torch.autograd.Function):
         d = ctx.d
         dt = _TORCH_DT[d.dtype]
         g = gy.to(dt).contiguous(memory_format=_CL)
-        dx = dw = db = None
-        ride_red = None
+        dx = dw = db = ride_red = None
         if ctx.needs_input_grad[0]:
             if crsk is None:
                 raise RuntimeError("sqr conv: backward-data for C<8 inputs is not supported")
-            addend = ctx.join.take() if (ctx.join is not None and ctx.role == "acc") else None
-            if isinstance(addend, MaskedGrad):
-                if (addend.dy.dtype == dt and addend.shape == (d.N, d.C, d.H, d.W) and d.R == 3 and d.S == 3
-                        and d.stride == 1 and d.pad == 1 and addend.dy.is_contiguous(memory_format=_CL)):
-                    dx = torch.empty((d.N, d.C, d.H, d.W), dtype=dt, device=g.device, memory_format=_CL)
-                    ws, n = _ws(d, 1, g.device)
-                    with _Probe("dgrad", d):
-                        rc = lib().sqr_conv2d_bwd_data_acc_masked(ptr(g), ptr(crsk), ptr(dx), ptr(addend.dy),
-                                                                  ptr(addend.mask), ctypes_ref(d), ptr(ws), n,
-                                                                  stream_ptr(g.device))
-                    if rc == 0:
-                        addend = _MaskedDone(dx)
-                    elif rc != -2:  # (-2: SQR_E_UNSUPPORTED -> mask, then the plain paths below)
-                        check(rc, "sqr_conv2d_bwd_data_acc_masked")
-                if isinstance(addend, MaskedGrad):
-                    addend = addend.full()
-            s2 = isinstance(addend, CompactS2)
-            if s2 and not (d.stride == 2 and addend.t.dtype == dt and addend.shape == (d.N, d.C, d.H, d.W)
-                           and tuple(addend.t.shape) == (d.N, d.C, d.H // 2, d.W // 2) and d.H % 2 == 0
-                           and d.W % 2 == 0 and addend.t.is_contiguous(memory_format=_CL)):
-                addend, s2 = addend.full(), False
-            link = ctx.bnb if (ctx.bnb is not None and ctx.bnb.ready() and addend is None) else None
-            deferred = ctx.deferred
-            if link is not None and link.x.dtype == dt and deferred is not None and link.deferred is deferred \
-                    and not deferred.y_written and (xin is None or xin.data_ptr() == deferred.y.data_ptr()):
-                # the input was applied on load without side outputs: the mask is recomputed here and
-                # the activation written for the weight gradient below
-                dx, link.stats = conv2d_bwd_data_bn_act(g, crsk, d, link.x, deferred.coef, link.mean, xin)
-                deferred.y_written = True
-                link.g = dx
-            elif link is not None and link.x.dtype == dt:
-                if deferred is not None:
-                    deferred.materialize()
-                dx, link.stats = conv2d_bwd_data_bn(g, crsk, d, link.x, link.mask, link.mean)
-                link.g = dx
-            elif isinstance(addend, _MaskedDone):
-                dx = addend.dx
-                ride_red = ctx.bnr  # dx is the whole gradient of x: its BatchNorm reduction can ride
-            elif s2:
-                dx = conv2d_bwd_data_acc_s2(g, crsk, d, addend.t)
-                ride_red = ctx.bnr  # dx is the whole gradient of x: its BatchNorm reduction can ride
-            elif addend is not None and addend.dtype == dt and addend.shape == (d.N, d.C, d.H, d.W) \
-                    and addend.is_contiguous(memory_format=_CL):
-                dx = conv2d_bwd_data_acc(g, crsk, d, addend)
-                ride_red = ctx.bnr  # dx is the whole gradient of x: its BatchNorm reduction can ride
-            elif ctx.join is not None and ctx.role == "dep" and not ctx.join.acc_done and d.R == 1 and d.S == 1 \
-                    and d.stride == 2 and d.pad == 0 and d.H % 2 == 0 and d.W % 2 == 0 and d.C >= 8:
-                # stride-2 1x1 downsample: only the (even, even) pixels of its input gradient are
-                # non-zero — computed as a stride-1 1x1 backward-data on the output grid and
-                # deposited compact for conv1's stride-2 backward-data (CompactS2)
-                d1 = _desc(d.N, d.C, d.H // 2, d.W // 2, d.K, 1, 1, 1, 0, dt)
-                dx = CompactS2(conv2d_bwd_data(g, crsk, d1).to(ctx.x_dtype), (d.N, d.C, d.H, d.W))
-            else:
-                dx = conv2d_bwd_data(g, crsk, d)
-                if addend is not None:
-                    dx = dx + addend
-            if not isinstance(dx, CompactS2):
-                dx = dx.to(ctx.x_dtype)
-            if ctx.join is not None and ctx.role == "dep":
-                dx = ctx.join.deposit(dx)
+            join, role = ctx.join, ctx.role
+            addend = join.take() if (join is not None and role == "acc") else None
+            route = dgrad_route(d, dt, addend, ctx.bnb, ctx.deferred, xin, join, role)
+            dx, whole = _dgrad_run(ctx, route, g, xin, crsk, addend)
+            ride_red = ctx.bnr if whole else None  # x's BatchNorm reduction can ride the weight gradient below
+            dx = dx.to(ctx.x_dtype)
+            if join is not None and role == "dep":
+                dx = join.deposit(dx)
                 if isinstance(dx, CompactS2):  # (not deposited: conv1's backward already ran)
                     dx = dx.full()
         if ctx.needs_input_grad[1]:

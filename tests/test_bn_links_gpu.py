@@ -667,6 +667,34 @@ def _expected_calls(chain, dtype):
     return dict(zip(LINK_CALLS, (3, 2, 0 if kind2 else 1, 1 if kind2 else 0)))
 
 
+# The six backward-data entries, counted next to the link calls: which of them each conv's input gradient
+# takes is the route choice of sqr.conv's backward.
+DGRAD_CALLS = ("sqr_conv2d_bwd_data", "sqr_conv2d_bwd_data_acc", "sqr_conv2d_bwd_data_acc_s2",
+               "sqr_conv2d_bwd_data_acc_masked", "sqr_conv2d_bwd_data_bn", "sqr_conv2d_bwd_data_bn_act")
+# (chain, 16-bit, direct): (linked run, plain run), each in DGRAD_CALLS' order; a call counts whether the
+# entry takes it or refuses it (with direct 0 sqr_conv2d_bwd_data_acc_masked refuses, and the addend goes
+# expanded through sqr_conv2d_bwd_data_acc).  Recorded from the code before the route choice became one
+# function.
+DGRAD_EXPECTED = {
+    ("id_id", False, 2): ((2, 0, 0, 0, 2, 0), (4, 0, 0, 0, 0, 0)),
+    ("id_id", False, 0): ((2, 0, 0, 0, 2, 0), (4, 0, 0, 0, 0, 0)),
+    ("id_id", True, 2): ((0, 0, 0, 2, 2, 0), (4, 0, 0, 0, 0, 0)),
+    ("id_id", True, 0): ((0, 2, 0, 2, 2, 0), (4, 0, 0, 0, 0, 0)),
+    ("id_ds", False, 2): ((3, 0, 0, 0, 2, 0), (5, 0, 0, 0, 0, 0)),
+    ("id_ds", False, 0): ((3, 0, 0, 0, 2, 0), (5, 0, 0, 0, 0, 0)),
+    ("id_ds", True, 2): ((1, 0, 1, 1, 2, 0), (5, 0, 0, 0, 0, 0)),
+    ("id_ds", True, 0): ((1, 1, 1, 1, 2, 0), (5, 0, 0, 0, 0, 0)),
+    ("ds_id", False, 2): ((3, 0, 0, 0, 2, 0), (5, 0, 0, 0, 0, 0)),
+    ("ds_id", False, 0): ((3, 0, 0, 0, 2, 0), (5, 0, 0, 0, 0, 0)),
+    ("ds_id", True, 2): ((1, 0, 1, 1, 0, 2), (5, 0, 0, 0, 0, 0)),
+    ("ds_id", True, 0): ((1, 1, 1, 1, 2, 0), (5, 0, 0, 0, 0, 0)),
+}
+
+
+def _expected_dgrad(chain, dtype, direct):
+    return tuple(dict(zip(DGRAD_CALLS, row)) for row in DGRAD_EXPECTED[chain, dtype != torch.float32, direct])
+
+
 def _make_chain(chain):
     from sqr.conv import Conv2d
     from sqr.resnet import BasicBlock
@@ -737,7 +765,7 @@ def test_block_chain(chain, dtype, direct, monkeypatch):
     base = _make_chain(chain)
     g = torch.Generator().manual_seed(len(chain) + shape[2])
     x0 = _rnd(torch.randn(shape, generator=g), dtype)
-    counts = dict.fromkeys(LINK_CALLS, 0)
+    counts = dict.fromkeys(LINK_CALLS + DGRAD_CALLS, 0)
 
     def counting(name):
         fn = getattr(L, name)
@@ -746,7 +774,7 @@ def test_block_chain(chain, dtype, direct, monkeypatch):
             counts[name] += 1
             return fn(*a)
         return wrapper
-    for name in LINK_CALLS:
+    for name in counts:
         monkeypatch.setattr(L, name, counting(name))
 
     old = L.sqr_conv_set_direct(direct)
@@ -770,6 +798,10 @@ def test_block_chain(chain, dtype, direct, monkeypatch):
         L.sqr_conv_set_direct(old)
 
     (yl, dxl, seql, nl), (yp, dxp, seqp, npl) = runs["linked"], runs["plain"]
+    dl, dp = ({k: n.pop(k) for k in DGRAD_CALLS} for n in (nl, npl))
+    print("dgrad_calls (%r, %r, %d): (%r, %r)," % (chain, dtype != torch.float32, direct, tuple(dl.values()),
+                                                   tuple(dp.values())))
+    assert (dl, dp) == _expected_dgrad(chain, dtype, direct)  # every input gradient took its route
     assert nl == _expected_calls(chain, dtype), nl  # the links fired ...
     assert nl["sqr_conv2d_bwd_weight_bn"] > 0 and nl["sqr_bn_bwd_apply"] > 0
     if dtype != torch.float32:
